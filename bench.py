@@ -3,8 +3,26 @@
 bench.py -- simulated cells x genes / second of the PROSSTT sampling hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--scaling weak|strong]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 (run without a launcher, ``--gpus N`` with N > 1 starts that launcher itself as a child process)
+
+A plain run does what the headline needs and nothing else: it builds the workload, ramps the clock, runs the W
+warmup steps, times the K steps, writes the outputs of the last timed step if ``--dump-outputs DIR`` is given,
+and prints the line.  ``--full`` adds every other measurement and check described below (the cold steps, the
+unchecked and plan-order steps, the first-moment check, north_star's shape, the achievable HBM rate, the
+end-to-end calls, the CPU baselines and, with N > 1, the gather, the pipeline and the strong-scaling
+configurations); the fields they fill are null in a plain run.
+
+``--dump-outputs DIR`` (after the timed steps, outside them): what the timed call returned in its last step --
+the count matrix and the global cell of each of its rows (device.PresentedCounts) -- as float64 ``.npy`` files,
+at most 64 MB in all: ``counts_sample`` (the rows of a fixed, seeded sample of cells, in increasing cell id),
+``counts_sample_cells`` (their cell ids), ``cell_totals`` (every cell's sum over genes, in increasing cell id),
+``gene_totals`` (every gene's sum over the rank's cells) and ``cell_of_row`` (the cell of each row as presented).
+Beyond 2^20 cells on a rank, ``cell_totals`` and ``cell_of_row`` keep the first 2^20 entries.  With N > 1 every
+rank writes its own shard's files, their names suffixed ``_rank<r>``, in a 1/N share of the 64 MB (fewer sampled
+rows, at most 2^20 / N entries per cell array).  The inputs depend on the arguments alone
+(every seed is fixed), so two builds can be compared file for file.
 
 Workload (BASELINE.json metric): config C3 -- 8-branch tree (T = 50 per branch, K = 25
 programs), 20 000 genes, 50 000 cells PER GPU; the tree goes through the product's own
@@ -14,21 +32,22 @@ from the tree's density.  A *step* = one pass of the fused count sampler
 rank's cells, all inputs resident in HBM, output left in HBM.  With N GPUs the plan is sharded by
 branch (prosstt_amd.parallel), no collective on the data path: 50 000 x N cells under
 ``--scaling weak`` (default), the configuration's own cell count under ``--scaling strong``
-(e.g. ``--config C4 --scaling strong``: 200 000 cells over the N GPUs).  With N > 1 the line also
-carries ``gather_ms`` (the one exchange of the path: count rows to rank 0, point-to-point) and
+(e.g. ``--config C4 --scaling strong``: 200 000 cells over the N GPUs).  With N > 1 and ``--full`` the line
+also carries ``gather_ms`` (the one exchange of the path: count rows to rank 0, point-to-point) and
 ``strong_scaling``: C4 (200 000 cells) and C5 (1 000 000 cells) split over the N GPUs.
 
 One JSON line on rank 0.
  * ``ms_per_step`` / ``value`` (= ``ms_per_step_strict``): the sampler as the product API calls it by default
    (``strict=True``: the reference's argument check rides in the call's own kernels, its verdict is read
-   behind the timed steps); ``ms_per_step_unchecked``: the same without the check; ``ms_per_step_cold``: the
-   first five steps of the process, before any clock ramp (what a user's first calls see).
+   behind the timed steps); ``ms_per_step_unchecked`` (``--full``): the same without the check;
+   ``ms_per_step_cold`` (``--full``): the first five steps of the process, before any clock ramp (what a user's
+   first calls see).
  * ``roofline``: the dominant kernel (k3::sample_counts_stream_kernel): algorithmic bytes per
    launch (DESIGN.md section 6) / its mean duration from HIP events on the launch stream;
    ``frac_whole_step`` prices the same bytes against ms_per_step (K3h, prep kernels, launch gaps
    included).  ``traffic`` comes from the committed rocprofv3 PMC passes and is reported only
    while the kernel sources are the ones that were profiled.
- * ``cpu_baseline`` (N = 1 only): the oracle's restatement of the reference's draw_counts WITH the
+ * ``cpu_baseline`` (``--full``, N = 1 only): the oracle's restatement of the reference's draw_counts WITH the
    reference's loop structure (oracle/ref_numpy.draw_counts_as_reference; within 1 % of the imported
    reference's time, tools/cpu_port_vs_reference.py) on a bounded sample of the same workload,
    1 core, as the reference is single-threaded; ``cpu_baseline_all_cores``: the same on one process
@@ -300,9 +319,11 @@ class Job:
             self.dist.destroy_process_group()
 
 
-def run_case(job, config, scaling, cells_per_gpu, steps, warmup, strict_steps, gather, ramp_ms=0.0):
+def run_case(job, config, scaling, cells_per_gpu, steps, warmup, strict_steps, gather, ramp_ms=0.0, full=True, dump_dir=None):
     """One workload on the job's ranks: W untimed + K timed passes of the count sampler over each rank's
-    shard (barrier + synchronize on both sides, max over ranks), optionally the row gather to rank 0."""
+    shard (barrier + synchronize on both sides, max over ranks), optionally the row gather to rank 0.
+    ``full``: also the cold steps, the unchecked and plan-order steps and the first-moment check.
+    ``dump_dir``: write what the last timed step returned there (dump_outputs)."""
     from prosstt_amd import parallel, workloads
     torch, ctx, world, rank = job.torch, job.ctx, job.world, job.rank
     work = workloads.build(config)          # the tree goes through the product's lineage stage (not part of the metric)
@@ -351,13 +372,15 @@ def run_case(job, config, scaling, cells_per_gpu, steps, warmup, strict_steps, g
 
     # The first steps of a process, before anything has loaded the device: idle clocks, cold code (reported as
     # ms_per_step_cold; a user's first calls see this, not the steady state below).
-    job.fence()
-    t0 = time.perf_counter()
-    for i in range(5):
-        step(3000 + i)
-    ctx.domain_status()
-    job.fence()
-    ms_cold = job.max_over_ranks(time.perf_counter() - t0) / 5 * 1e3
+    ms_cold = None
+    if full:
+        job.fence()
+        t0 = time.perf_counter()
+        for i in range(5):
+            step(3000 + i)
+        ctx.domain_status()
+        job.fence()
+        ms_cold = job.max_over_ranks(time.perf_counter() - t0) / 5 * 1e3
     # The device comes out of the (mostly host-side) setup at idle clocks and takes a few hundred ms of load to
     # reach the clock it then holds (measured: the same kernel 1.88 ms in the first 3 steps, 1.63 ms after 60);
     # the W warmup steps of the contract are too short for that, so untimed passes of the same step run first.
@@ -383,9 +406,13 @@ def run_case(job, config, scaling, cells_per_gpu, steps, warmup, strict_steps, g
     res = dict(work=work, plan=(pt, br, sc), G=G, n_total=n_total, per_gpu=per_gpu, cells_on_rank=int(len(mine)),
                ms_per_step=elapsed / steps * 1e3, value=n_total * G / (elapsed / steps), kernel_ms=kms,
                rows_total=work.info["resident_rows"], ms_unchecked=None, ms_cold=ms_cold, gather_ms=None,
-               ramp_calls=ramp_calls, plan_order_ms=plan_order_ms)
+               ramp_calls=ramp_calls, plan_order_ms=plan_order_ms, ratio=None)
+    if dump_dir is not None:
+        dump_outputs(dump_dir, out, mine, "" if world == 1 else "_rank%d" % rank, ranks=world)
 
     # the same steps without the domain check (strict=False)
+    if not full:
+        strict_steps = 0
     if strict_steps > 0:
         step(99, strict=False)
         job.fence()
@@ -415,15 +442,52 @@ def run_case(job, config, scaling, cells_per_gpu, steps, warmup, strict_steps, g
         step(97)                      # (leaves `out` as the timed steps wrote it: the sanity check below goes by d_rows)
 
     # sanity inside the bench: first moment of this rank's shard (catches a silently dead kernel)
-    mu_sum = float((means.double().sum(dim=1)[d_rows.long()] * d_sc).sum())
-    x_sum = sum(int(out[lo:lo + 16384].sum(dtype=torch.int64)) for lo in range(0, len(mine), 16384))   # bounded temporaries
-    res["ratio"] = x_sum / mu_sum if mu_sum > 0 else float("nan")
+    if full:
+        mu_sum = float((means.double().sum(dim=1)[d_rows.long()] * d_sc).sum())
+        x_sum = sum(int(out[lo:lo + 16384].sum(dtype=torch.int64)) for lo in range(0, len(mine), 16384))   # bounded temporaries
+        res["ratio"] = x_sum / mu_sum if mu_sum > 0 else float("nan")
     res["tree"] = tree
     if gather and world > 1:
         time_gather(job, res, out, mine)
     else:
         res["shard"] = (out, mine)          # for a later time_gather (the main case: after the line is assembled)
     return res
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 2024            # the sample of cells in counts_sample: fixed, so that two runs pick the same rows
+DUMP_MAX_CELLS = 1 << 20
+
+
+def dump_outputs(out_dir, out, cell_of_row, suffix="", ranks=1):
+    """What the timed call returned in its last step -- the (cells, G) int32 count matrix in HBM and the global cell of
+    each of its rows -- as float64 .npy files under ``out_dir`` (the module docstring lists them).  Everything but
+    ``cell_of_row`` is keyed by cell id, so the files do not depend on the order in which the cells were presented.
+    ``ranks``: how many ranks share the 64 MB (each writes its own shard's files)."""
+    import torch
+    n, G = out.shape
+    cell_of_row = np.asarray(cell_of_row, dtype=np.int64)
+    by_cell = np.argsort(cell_of_row, kind="stable")            # rows in increasing cell id
+    row_totals, gene_totals = [], torch.zeros(G, dtype=torch.int64, device=out.device)
+    for lo in range(0, n, 8192):                                # bounded temporaries
+        blk = out[lo:lo + 8192]
+        row_totals.append(blk.sum(dim=1, dtype=torch.int64))
+        gene_totals += blk.sum(dim=0, dtype=torch.int64)
+    row_totals = torch.cat(row_totals).cpu().numpy()
+    k = min(256, n, max(1, (4 << 20) // (G * ranks)))           # at most 32 MB of float64 counts over all ranks
+    pick = by_cell[np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))]
+    sample = out[torch.as_tensor(pick, dtype=torch.int64, device=out.device)].to(torch.float64).cpu().numpy()
+    arrays = {"counts_sample": sample,
+              "counts_sample_cells": cell_of_row[pick].astype(np.float64),
+              "cell_totals": row_totals[by_cell][:DUMP_MAX_CELLS // ranks].astype(np.float64),
+              "gene_totals": gene_totals.cpu().numpy().astype(np.float64),
+              "cell_of_row": cell_of_row[:DUMP_MAX_CELLS // ranks].astype(np.float64)}
+    nbytes = sum(a.nbytes for a in arrays.values())
+    if nbytes > DUMP_MAX_BYTES // ranks:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte share of this rank" % (nbytes, DUMP_MAX_BYTES // ranks))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 def hbm_achievable(job, n_cells, G, reps=10):
@@ -545,7 +609,15 @@ def main():
                          "does not order its cells gets; simulation.draw_counts groups them)")
     ap.add_argument("--no-end-to-end", action="store_true",
                     help="skip the end-to-end time of the drop-in sample_density call (N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline: cold, unchecked and plan-order steps, the "
+                         "first-moment check, north_star's shape, the achievable HBM rate, the end-to-end calls, the CPU "
+                         "baselines; with N > 1 the gather, the pipeline and the strong-scaling configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))      # before anything here has touched torch.cuda
@@ -557,16 +629,15 @@ def main():
     job = Job(args)
     world, rank = job.world, job.rank
     main_case = run_case(job, args.config, args.scaling, args.cells_per_gpu, args.steps, args.warmup,
-                         args.strict_steps, gather=False, ramp_ms=args.ramp_ms)
+                         args.strict_steps, gather=False, ramp_ms=args.ramp_ms, full=args.full, dump_dir=args.dump_outputs)
     work, G, n_total = main_case["work"], main_case["G"], main_case["n_total"]
-    pt, br, sc = main_case["plan"]
 
     # BASELINE.json's north_star quotes its target ("at >= 40 % HBM roofline on 1 MI355X") on a 32-branch tree at the
     # headline's size; the metric's own configuration (configs[2], the headline above) is the 8-branch tree.  The default
-    # 1-GPU run therefore carries that shape too, under "north_star_shape" (the same step, the same timing rules).
+    # 1-GPU run with --full therefore carries that shape too, under "north_star_shape" (the same step, the same timing rules).
     target_case = None
     default_shape = args.config == "C3" and args.cells_per_gpu is None and args.scaling == "weak" and world == 1
-    if default_shape and not args.no_target_shape:
+    if args.full and default_shape and not args.no_target_shape:
         target_case = run_case(job, "T32", "weak", None, args.steps, args.warmup, 0, gather=False, ramp_ms=min(args.ramp_ms, 150.0))
         target_case.pop("shard", None)
     main_case["target_case"] = target_case
@@ -575,12 +646,12 @@ def main():
     main_case["achievable"] = None
     if world == 1:
         main_case.pop("shard", None)
-        if 8.0 * main_case["cells_on_rank"] * G < 0.4 * job.torch.cuda.get_device_properties(job.ctx.device).total_memory:
+        if args.full and 8.0 * main_case["cells_on_rank"] * G < 0.4 * job.torch.cuda.get_device_properties(job.ctx.device).total_memory:
             main_case["achievable"] = hbm_achievable(job, main_case["cells_on_rank"], G)
-    if world == 1 and not args.no_end_to_end and rank == 0:
+    if args.full and world == 1 and not args.no_end_to_end and rank == 0:
         end_to_end = tuple(end_to_end_ms(main_case["tree"], work, n_total, out) for out in ("numpy", "numpy32", "csr"))
 
-    # With N > 1 the measurements beyond the contract's line (the row gather, the strong-scaling configurations)
+    # With N > 1 and --full the measurements beyond the contract's line (the row gather, the strong-scaling configurations)
     # run under a watchdog: if one of them raises or stalls, rank 0 still prints the line -- with what was
     # measured and the reason under "extras_error" -- and every rank leaves with exit code 0.
     strong, extras_error = [], None
@@ -595,7 +666,7 @@ def main():
 
     guard = ExtrasGuard(rank, float(os.environ.get("PROSSTT_BENCH_EXTRAS_TIMEOUT_S", "600")),
                         exit_code=3 if args.fail_on_extras_error else 0)
-    if world > 1:
+    if args.full and world > 1:
         guard.arm(lambda why: emit(why))
         try:
             if not args.no_gather:
@@ -707,7 +778,7 @@ def assemble_line(args, job, main_case, strong, end_to_end, extras_error):
                    "lineage_attempts": work.info["attempts"], "lineage_s": round(work.info["lineage_s"], 3),
                    "lineage_sharded_by_genes": bool(work.info["sharded"]),
                    "clock_ramp": "%d untimed passes (%.0f ms) before the %d warmup steps" % (main_case["ramp_calls"], args.ramp_ms, args.warmup),
-                   "cold_steps": 5,
+                   "cold_steps": 5 if args.full else 0,
                    "presentation": "plan order" if args.plain_order else
                                    "cells grouped by mean-tensor row (simulation.draw_counts' call: prosstt_amd_plan_order); rows of "
                                    "the matrix in that order, put back in plan order inside the copy to the host",
@@ -719,7 +790,7 @@ def assemble_line(args, job, main_case, strong, end_to_end, extras_error):
                    "plan_order_host_ms": main_case.get("plan_order_ms"),
                    "library_version": _library_version(), "sampler_definition": "PRNB-7",
                    "gcn_arch": job.torch.cuda.get_device_properties(job.ctx.device).gcnArchName,
-                   "sum_counts_over_sum_means": round(main_case["ratio"], 5)},
+                   "sum_counts_over_sum_means": None if main_case["ratio"] is None else round(main_case["ratio"], 5)},
         "roofline": {"bound": "hbm", "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK, "traffic": traffic, "traffic_source": traffic_src,
                      "kernel": "k3::sample_counts_stream_kernel<%s, %s>" % (
@@ -767,11 +838,11 @@ def assemble_line(args, job, main_case, strong, end_to_end, extras_error):
         line["strong_scaling"] = strong
     if end_to_end is not None:
         line["end_to_end_ms"], line["end_to_end_ms_int32"], line["end_to_end_ms_csr"] = end_to_end
-    if world == 1 and args.cpu_cells > 0:
+    if args.full and world == 1 and args.cpu_cells > 0:
         line["cpu_baseline"] = cpu_baseline(work, pt, br, sc, min(args.cpu_cells, n_total))
         line["speedup_vs_cpu_1core"] = main_case["value"] / line["cpu_baseline"]["value"]
     procs = physical_cores() if args.cpu_procs < 0 else args.cpu_procs
-    if world == 1 and args.cpu_cells > 0 and procs > 1:
+    if args.full and world == 1 and args.cpu_cells > 0 and procs > 1:
         line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(
             work, pt, br, sc, min(max(args.cpu_cells, 250 * procs), n_total), procs)
     if extras_error:

@@ -7,8 +7,8 @@ ARGS="bench.py --steps 10 --warmup 2 --cpu-cells 0 --no-end-to-end --no-target-s
 python3 $ARGS 2> $O/unprofiled.err | tail -1 > $O/bench_unprofiled.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $ARGS 2> $O/trace.err | tail -1 > $O/bench_under_rocprof.json
 python3 $ARGS --config T32 2> $O/unprofiled_t32.err | tail -1 > $O/t32_bench_unprofiled.json
-python3 bench.py 2> $O/default.err | tail -1 > $O/bench_default.json
-python3 bench.py 2> $O/default2.err | tail -1 > $O/bench_default_second_run.json
+python3 bench.py --full 2> $O/default.err | tail -1 > $O/bench_default.json
+python3 bench.py --full 2> $O/default2.err | tail -1 > $O/bench_default_second_run.json
 python3 -c "
 import json
 for f in ('bench_unprofiled', 'bench_under_rocprof', 't32_bench_unprofiled', 'bench_default', 'bench_default_second_run'):

@@ -5,8 +5,8 @@ timeout 2400 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; tail 
 timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
 bash tools/profile_bench.sh $TAG > /dev/null 2>&1; grep "under the tracer\|derived" -A2 gpurun_out/prof_$TAG/summary.txt | cut -c1-300
 BENCH_EXTRA="--config T32" bash tools/profile_bench.sh ${TAG}_t32 > /dev/null 2>&1; grep "under the tracer\|derived" -A2 gpurun_out/prof_${TAG}_t32/summary.txt | cut -c1-300
-python3 bench.py 2> $O/bench_default.err | tail -1 > $O/bench_default.json
-PROSSTT_BENCH_BACKEND=gloo PROSSTT_BENCH_ONE_GPU=1 timeout 900 python3 bench.py --gpus 2 --steps 5 --warmup 2 2> $O/bench2.err | tail -1 > $O/bench_2ranks_gloo_one_gpu.json
+python3 bench.py --full 2> $O/bench_default.err | tail -1 > $O/bench_default.json
+PROSSTT_BENCH_BACKEND=gloo PROSSTT_BENCH_ONE_GPU=1 timeout 900 python3 bench.py --gpus 2 --steps 5 --warmup 2 --full 2> $O/bench2.err | tail -1 > $O/bench_2ranks_gloo_one_gpu.json
 {
 echo "# cells presented grouped by mean-tensor row (KBENCH_SORT=1: what simulation.draw_counts does), 20 calls back to back per round:"
 for c in C3 T32 C2 C4 C5; do if [ $c = C5 ]; then export KBENCH_CELLS=125000; else unset KBENCH_CELLS; fi; KBENCH_SORT=1 KBENCH_BURST=20 timeout 600 python3 tools/kbench_ab.py $c 8 shipped build/ab/libprosstt_amd_r5.so 2>&1 | grep -v amdgpu; done
