@@ -5,6 +5,10 @@ Drop-in for the reference package's modules:
 
     from prosstt_amd import tree, simulation as sim, sim_utils as sut, count_model as cm
 
+Count-matrix summaries on the device (means, variances, zeros, library sizes; no host copy of the matrix):
+
+    from prosstt_amd import summary
+
 or, for unmodified scripts that say ``from prosstt import ...``:
 
     import prosstt_amd; prosstt_amd.install_as_prosstt()

@@ -37,6 +37,12 @@ HOST_SYMBOLS = ["prosstt_amd_host_widen_i32_i64", "prosstt_amd_host_widen_u16_i6
                 "prosstt_amd_host_has_avx2"]
 
 
+STATS_LIB_PATH = os.environ.get("PROSSTT_AMD_STATS_LIB") or os.path.join(_HERE, "lib", "libprosstt_amd_stats.so")
+# every symbol include/prosstt_amd_stats.h declares
+STATS_SYMBOLS = ["prosstt_amd_stats_last_error", "prosstt_amd_stats_workspace_bytes", "prosstt_amd_stats_count_summary"]
+STATS_ACCUMULATE = 1
+
+
 class NativeError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("prosstt_amd error %d: %s" % (code, message))
@@ -69,6 +75,37 @@ def load_host():
         L.prosstt_amd_host_has_avx2.restype = ctypes.c_int
         _host_lib = L
         return L
+
+
+_stats_lib = None
+
+
+def load_stats():
+    """libprosstt_amd_stats.so (include/prosstt_amd_stats.h: summary statistics of a device count matrix), once.  Raises if
+    it has not been built."""
+    global _stats_lib
+    with _lock:
+        if _stats_lib is not None:
+            return _stats_lib
+        if not os.path.exists(STATS_LIB_PATH):
+            raise RuntimeError("%s not found: build it with `make -C prosstt_amd/csrc/stats` (or "
+                               "`python -c 'import __graft_entry__ as g; g.build()'`). prosstt_amd has no "
+                               "CPU fallback." % STATS_LIB_PATH)
+        import torch  # noqa: F401    (torch's HIP runtime first: see load())
+        L = ctypes.CDLL(STATS_LIB_PATH)
+        vp, i64, u32, u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64
+        L.prosstt_amd_stats_last_error.restype = ctypes.c_char_p
+        L.prosstt_amd_stats_workspace_bytes.argtypes = [i64, i64, ctypes.POINTER(u64)]
+        L.prosstt_amd_stats_workspace_bytes.restype = ctypes.c_int
+        L.prosstt_amd_stats_count_summary.argtypes = [vp, vp, i64, i64, i64, vp, u64, vp, vp, vp, vp, vp, vp, u32]
+        L.prosstt_amd_stats_count_summary.restype = ctypes.c_int
+        _stats_lib = L
+        return L
+
+
+def check_stats(code):
+    if code != OK:
+        raise NativeError(code, load_stats().prosstt_amd_stats_last_error().decode("utf-8", "replace"))
 
 
 def load():
