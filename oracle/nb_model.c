@@ -774,6 +774,120 @@ PRNB_EXPORT PRNB_CLONES void prnb_lineage_walk(uint64_t seed, uint64_t sid, int3
     }
 }
 
+/*
+ * Lineage statistics ("K2", prosstt_amd.hip: lineage_attempt_*_kernel, lineage_commit_kernel and the host entry
+ * prosstt_amd_lineage_attempt_batch) in the kernels' order of binary64 operations, so that the device's maxima,
+ * anticorrelated-gene counts, relative means and per-gene maxima equal this model's bit for bit:
+ *   x_t[g] = programs[t] . H[:, g]:  acc = 0; for k = 0..K-1: acc = fma(P[t][k], H[k][g], acc)
+ *   centring (the host's centred()): mean = sequential sum over the first `steps` rows / steps; P - mean
+ *   per sibling j, common = min(T, T_j), both series truncated to `common` steps and centred over them; per gene four
+ *   chunks [c*common/4, (c+1)*common/4) accumulate cov = fma(x, y, cov), vx = fma(x, x, vx), vy = fma(y, y, vy)
+ *   from 0, combined as ((p0 + p1) + p2) + p3; the gene counts iff cov < 0 && vx > 0 && vy > 0.
+ * A NaN in the inputs is outside the contract (the kernels' fmax drops it where numpy's max would return it).
+ */
+static inline double lin_dot(const double* row, int32_t K, const double* H, int64_t G, int64_t g)
+{
+    double acc = 0.0;
+    for (int32_t k = 0; k < K; ++k) acc = fma(row[k], H[(int64_t)k * G + g], acc);
+    return acc;
+}
+
+static void lin_centred(const double* src, int32_t steps, int32_t K, double* dst)
+{
+    for (int32_t k = 0; k < K; ++k) {
+        double mean = 0.0;
+        for (int32_t t = 0; t < steps; ++t) mean += src[(int64_t)t * K + k];
+        mean /= steps;
+        for (int32_t t = 0; t < steps; ++t) dst[(int64_t)t * K + k] = src[(int64_t)t * K + k] - mean;
+    }
+}
+
+/* B attempts (programs [B][T][K]) against n_sib siblings stored back to back in `sibs` ([sib_T[j]][K] each):
+ * out_max[b] = max over t, g of x_t[g];  out_counts[b*n_sib + j] = anticorrelated genes against sibling j. */
+PRNB_EXPORT PRNB_CLONES void prnb_lineage_attempt(const double* programs, int32_t B, int32_t T, int32_t K,
+                                                  const double* H, int64_t G, int32_t n_sib, const double* sibs,
+                                                  const int32_t* sib_T, double* out_max, int64_t* out_counts)
+{
+    int64_t at, len = 0;
+    for (int32_t j = 0; j < n_sib; ++j) len += 2 * (int64_t)(T < sib_T[j] ? T : sib_T[j]) * K;
+    double* cen = (double*)malloc(sizeof(double) * (size_t)(len > 0 ? len : 1));     /* [current | sibling] per j */
+    double* gmax = (double*)malloc(sizeof(double) * (size_t)(G > 0 ? G : 1));
+    uint8_t* neg = (uint8_t*)malloc((size_t)(G > 0 ? G : 1) * (size_t)(n_sib > 0 ? n_sib : 1));
+    if (!cen || !gmax || !neg) { fprintf(stderr, "prnb_lineage_attempt: out of memory\n"); abort(); }
+    at = 0;
+    for (int32_t j = 0; j < n_sib; ++j) {                                               /* siblings: once */
+        const int32_t common = T < sib_T[j] ? T : sib_T[j];
+        const double* s = sibs;
+        for (int32_t i = 0; i < j; ++i) s += (int64_t)sib_T[i] * K;
+        lin_centred(s, common, K, cen + at + (int64_t)common * K);
+        at += 2 * (int64_t)common * K;
+    }
+    for (int32_t b = 0; b < B; ++b) {
+        const double* P = programs + (int64_t)b * T * K;
+        at = 0;
+        for (int32_t j = 0; j < n_sib; ++j) {
+            const int32_t common = T < sib_T[j] ? T : sib_T[j];
+            lin_centred(P, common, K, cen + at);
+            at += 2 * (int64_t)common * K;
+        }
+#pragma omp parallel for schedule(dynamic, 16)
+        for (int64_t g = 0; g < G; ++g) {
+            double mx = -INFINITY;
+            for (int32_t t = 0; t < T; ++t) mx = fmax(mx, lin_dot(P + (int64_t)t * K, K, H, G, g));
+            gmax[g] = mx;
+            int64_t off = 0;
+            for (int32_t j = 0; j < n_sib; ++j) {
+                const int32_t common = T < sib_T[j] ? T : sib_T[j];
+                const double* pc = cen + off;
+                const double* ps = pc + (int64_t)common * K;
+                off += 2 * (int64_t)common * K;
+                double cov = 0.0, vx = 0.0, vy = 0.0;
+                for (int c = 0; c < 4; ++c) {
+                    double pcov = 0.0, pvx = 0.0, pvy = 0.0;
+                    for (int32_t t = (c * common) / 4; t < ((c + 1) * common) / 4; ++t) {
+                        const double x = lin_dot(pc + (int64_t)t * K, K, H, G, g);
+                        const double y = lin_dot(ps + (int64_t)t * K, K, H, G, g);
+                        pcov = fma(x, y, pcov);
+                        pvx = fma(x, x, pvx);
+                        pvy = fma(y, y, pvy);
+                    }
+                    if (c == 0) { cov = pcov; vx = pvx; vy = pvy; }
+                    else { cov += pcov; vx += pvx; vy += pvy; }
+                }
+                neg[g * n_sib + j] = cov < 0.0 && vx > 0.0 && vy > 0.0;
+            }
+        }
+        double mx = -INFINITY;
+        for (int64_t g = 0; g < G; ++g) mx = fmax(mx, gmax[g]);
+        out_max[b] = mx;
+        for (int32_t j = 0; j < n_sib; ++j) {
+            int64_t n = 0;
+            for (int64_t g = 0; g < G; ++g) n += neg[g * n_sib + j];
+            out_counts[(int64_t)b * n_sib + j] = n;
+        }
+    }
+    free(cen);
+    free(gmax);
+    free(neg);
+}
+
+/* Commit of an accepted branch: rel[t][g] = x_t[g] (rel may be NULL) and gene_max[g] = max(gene_max[g], max_t
+ * rel[t][g]) (gene_max may be NULL; the device's compare-and-swap keeps the old value unless the new one is larger). */
+PRNB_EXPORT PRNB_CLONES void prnb_lineage_commit(const double* programs, int32_t T, int32_t K, const double* H,
+                                                 int64_t G, double* rel, double* gene_max)
+{
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t g = 0; g < G; ++g) {
+        double mx = -INFINITY;
+        for (int32_t t = 0; t < T; ++t) {
+            const double x = lin_dot(programs + (int64_t)t * K, K, H, G, g);
+            if (rel) rel[(int64_t)t * G + g] = x;
+            mx = fmax(mx, x);
+        }
+        if (gene_max && mx > gene_max[g]) gene_max[g] = mx;
+    }
+}
+
 /* n draws from one parameter set (law tests): cell = first_cell + i, gene fixed. */
 PRNB_EXPORT PRNB_CLONES void prnb_sample_iid(float m, double a, double b, uint64_t seed,
                                              uint64_t first_cell, uint32_t gene, int64_t n,

@@ -59,6 +59,12 @@ def lib():
                                       ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int64, _i32p]
         L.prnb_lineage_walk.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, _f64p]
         L.prnb_lineage_walk.restype = None
+        L.prnb_lineage_attempt.argtypes = [_f64p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _f64p, ctypes.c_int64,
+                                           ctypes.c_int32, _f64p, _i32p, _f64p, _i64p]
+        L.prnb_lineage_attempt.restype = None
+        L.prnb_lineage_commit.argtypes = [_f64p, ctypes.c_int32, ctypes.c_int32, _f64p, ctypes.c_int64,
+                                          ctypes.c_void_p, ctypes.c_void_p]
+        L.prnb_lineage_commit.restype = None
         for f in (L.prnb_philox, L.prnb_math, L.prnb_sample_counts, L.prnb_nb_params, L.prnb_sample_iid):
             f.restype = None
         _LIB = L
@@ -262,3 +268,37 @@ def lineage_walk(seed, sid, T, K):
     out = np.empty((T, K), np.float64)
     lib().prnb_lineage_walk(seed, sid, T, K, out)
     return out
+
+
+def lineage_attempt(programs, H, sibs=()):
+    """Model of the K2 attempt kernels: programs (B, T, K), H (K, G), sibling programs (T_j, K) ->
+    (max of programs[b] @ H as (B,), anticorrelated-gene counts as (B, n_sib) int64), bit for bit the device's."""
+    P = np.ascontiguousarray(programs, np.float64)
+    B, T, K = P.shape
+    H = np.ascontiguousarray(H, np.float64)
+    if H.ndim != 2 or H.shape[0] != K:
+        raise ValueError("H must be (K, G)")
+    sibs = [np.ascontiguousarray(s, np.float64) for s in sibs]
+    if any(s.ndim != 2 or s.shape[1] != K or s.shape[0] < 1 for s in sibs):
+        raise ValueError("sibling programs must be (T_j >= 1, K)")
+    flat = np.concatenate([s.ravel() for s in sibs]) if sibs else np.zeros(1)
+    lens = np.array([s.shape[0] for s in sibs] or [0], np.int32)
+    top = np.empty(B, np.float64)
+    counts = np.zeros((B, max(len(sibs), 1)), np.int64)
+    lib().prnb_lineage_attempt(P, B, T, K, H, H.shape[1], len(sibs), flat, lens, top, counts)
+    return top, counts[:, :len(sibs)]
+
+
+def lineage_commit(programs, H, prior_gene_max=None):
+    """Model of the K2 commit kernels: programs (T, K), H (K, G) -> (rel (T, G), gene_max (G,)) with
+    gene_max = max(prior_gene_max (default -inf), max over t of rel), bit for bit the device's."""
+    P = np.ascontiguousarray(programs, np.float64)
+    T, K = P.shape
+    H = np.ascontiguousarray(H, np.float64)
+    if H.ndim != 2 or H.shape[0] != K:
+        raise ValueError("H must be (K, G)")
+    G = H.shape[1]
+    rel = np.empty((T, G), np.float64)
+    gmax = np.full(G, -np.inf) if prior_gene_max is None else np.array(prior_gene_max, np.float64, copy=True).reshape(G)
+    lib().prnb_lineage_commit(P, T, K, H, G, rel.ctypes.data_as(ctypes.c_void_p), gmax.ctypes.data_as(ctypes.c_void_p))
+    return rel, gmax

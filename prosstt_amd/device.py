@@ -214,11 +214,14 @@ class Context:
         (max(programs[b]@H) as (B,) float64, #genes with r<0 per sibling as (B, n_sib) int64)
         -- simulation.py:269-272 per attempt."""
         programs = np.ascontiguousarray(programs, np.float64)
+        if programs.ndim != 3:
+            raise ValueError("programs must be (B, T, K)")
         B, T, K = programs.shape
+        H = self._coefficients(H, K)
         sibs = [np.ascontiguousarray(s, np.float64) for s in sib_programs]
         n = len(sibs)
         for s in sibs:
-            if s.shape[1] != K:
+            if s.ndim != 2 or s.shape[1] != K:
                 raise ValueError("sibling programs must have %d columns" % K)
         ptrs = (ctypes.c_void_p * max(n, 1))(*[s.ctypes.data for s in sibs])
         lens = (ctypes.c_int32 * max(n, 1))(*[s.shape[0] for s in sibs])
@@ -257,25 +260,72 @@ class Context:
         return out
 
     def lineage_commit(self, programs, H, rel_out=None, gene_max=None):
+        """rel_out = programs @ H and gene_max = max(gene_max, max over rows of rel) on the device (either may be None);
+        ``rel_out`` (T, G) and ``gene_max`` (G,) must be contiguous binary64 tensors on this context's device."""
+        torch = _torch()
         programs = np.ascontiguousarray(programs, np.float64)
+        if programs.ndim != 2:
+            raise ValueError("programs must be (T, K)")
         T, K = programs.shape
+        H = self._coefficients(H, K)
+        G = H.shape[1]
+        self._output(rel_out, "rel_out", torch.float64, (T, G))
+        self._output(gene_max, "gene_max", torch.float64, (G,))
         _native.check(self._lib.prosstt_amd_lineage_commit(
             self._h, programs.ctypes.data_as(ctypes.c_void_p), T, K, _ptr(H), H.shape[1],
             _ptr(rel_out), _ptr(gene_max)))
 
     def gene_max(self, rel, gene_max):
         """gene_max[g] = max(gene_max[g], max over rows of rel[:, g]) -- sim_utils.py:423-425 in log space."""
-        rel = rel.contiguous()
-        _native.check(self._lib.prosstt_amd_gene_max(self._h, _ptr(rel), rel.shape[0], rel.shape[1], _ptr(gene_max)))
+        torch = _torch()
+        rel = self.tensor(rel, torch.float64)
+        if rel.dim() != 2:
+            raise ValueError("rel must be (rows, G)")
+        self._output(gene_max, "gene_max", torch.float64, (rel.shape[1],))
+        if rel.numel():                           # (an empty tensor has no data pointer to pass)
+            _native.check(self._lib.prosstt_amd_gene_max(self._h, _ptr(rel), rel.shape[0], rel.shape[1], _ptr(gene_max)))
         return gene_max
 
     def means_from_rel(self, rel, base, out=None):
+        """float32 (rows, G) device tensor exp(rel) * base (one rounding of the binary64 value; a positive mean below
+        binary32's smallest normal is stored as that); ``out`` must be a contiguous float32 tensor on this device."""
         torch = _torch()
+        rel = self.tensor(rel, torch.float64)
+        if rel.dim() != 2:
+            raise ValueError("rel must be (rows, G)")
         rows, G = rel.shape
+        base = self.tensor(base, torch.float64)
+        if base.shape != (G,):
+            raise ValueError("base must have one entry per gene")
         if out is None:
             out = torch.empty((rows, G), dtype=torch.float32, device=self.torch_device)
-        _native.check(self._lib.prosstt_amd_means_from_rel(self._h, _ptr(rel), _ptr(base), rows, G, _ptr(out)))
+        self._output(out, "out", torch.float32, (rows, G))
+        if out.numel():
+            _native.check(self._lib.prosstt_amd_means_from_rel(self._h, _ptr(rel), _ptr(base), rows, G, _ptr(out)))
         return out
+
+    def _coefficients(self, H, K):
+        """H as a contiguous (K, G) binary64 device tensor (the kernels index it as H + k*G + g)."""
+        H = self.tensor(H, _torch().float64)
+        if H.dim() != 2 or H.shape[0] != K or H.shape[1] == 0:
+            raise ValueError("H must be (%d, G >= 1), not %s" % (K, tuple(H.shape)))
+        return H
+
+    def _output(self, t, name, dtype, shape):
+        """Refuse (on the host, before any launch) an output the kernels could not write as they index it."""
+        if t is None:
+            return
+        torch = _torch()
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch tensor on %s" % (name, self.torch_device))
+        if t.device != self.torch_device:
+            raise ValueError("%s is on %s, not on %s" % (name, t.device, self.torch_device))
+        if t.dtype != dtype:
+            raise TypeError("%s must be %s, not %s" % (name, dtype, t.dtype))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("%s must have shape %s, not %s" % (name, tuple(shape), tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
 
 
 def plan_order(row_of_cell, rows=None):
