@@ -6,8 +6,9 @@ call into libprosstt_amd.so.  Nothing here computes on the CPU.
 """
 import ctypes
 import os
-import sys
 import threading
+import warnings
+import weakref
 
 import numpy as np
 
@@ -370,316 +371,113 @@ PINNED_RETURN_MAX = int(os.environ.get("PROSSTT_AMD_PINNED_MAX_BYTES", str(32 <<
 HOST_DTYPES = {"numpy": np.int64, "numpy32": np.int32, "numpy16": np.uint16}
 
 
+# How an int64 / int32 host return of 2^24 counts or more travels.  WIDEN_ON = "host" (default): the matrix crosses PCIe in
+# a wire format narrower than its type -- first "u8", the low 8 bits of every count, and beside them the entries that
+# have higher bits set (two thirds of a count matrix are zeros; one count in a thousand of C3 is above 255, the largest is
+# 84 036); "u16", then "i32", for a matrix with too many of those -- and the host library's threads (libprosstt_amd_host.so)
+# widen chunk i - 1 into the result while chunk i is on the bus; "device": as rounds 2 to 5 did -- int64 formed on the
+# device, 8 bytes per count over PCIe, int32 copied as it lies (the choice for a host with very few cores).
+# (tools/host_widen_probe.py, tools/e2e_threads.py on an MI355X box's host: the pool writes 250 - 340 GB/s from eight threads
+# on; PCIe carries 52 GB/s.  C3 end to end: int64 147 -> 39 - 51 ms, int32 76 -> 32 - 39 ms, out="csr" 58 -> 38 ms.)
+WIDEN_ON = os.environ.get("PROSSTT_AMD_WIDEN", "host")
+HOST_THREADS = int(os.environ.get("PROSSTT_AMD_HOST_THREADS", str(max(1, min(16, os.cpu_count() or 1)))))
+
+
 def to_host(counts, dtype=np.int64, chunk_bytes=256 << 20, row_order=None):
     """int32 device counts -> host ndarray of ``dtype``: int64 (the reference's return type,
     simulation.py:651), int32 (what the device holds) or uint16 (raises OverflowError if a count does not fit: C3's
     largest is 84 036).
 
-    int64 and int32 of 2^24 counts or more (``_to_host_widened``): the matrix travels a chunk of rows at a time by
-    asynchronous copies on a second stream, in a WIRE format -- the low 8 (or 16) bits of every count, the few entries with
-    higher bits set beside them as (position, value) pairs, or the int32 as it lies (``WIRE``) -- into two page-locked
-    bounce buffers, and the host library's threads widen chunk i - 1 into the result while chunk i is on the bus; the
-    result lies in pageable memory on huge pages that is recycled once the caller has dropped it (``RESULT_MEMORY``,
-    ``_result_array``).  Everything else -- uint16, smaller matrices, ``WIDEN_ON`` = "device" -- as until round 5: the
-    chunks land by DMA straight in a page-locked result from torch's caching host allocator (at most
-    PROSSTT_AMD_PINNED_MAX_BYTES, default 32 GiB; beyond that, or when page-locking fails, in ordinary memory); int64 is
-    formed and uint16 narrowed on the device, chunk by chunk (two staging buffers) under the transfer of the previous chunk,
-    int32 is copied as it lies.
+    int64 and int32 of 2^24 counts or more cross PCIe a chunk of rows at a time in a wire format narrower than the result
+    (``WIDEN_ON``) and are widened by the host library's threads into pageable memory on huge pages that is recycled once
+    the caller has dropped the result (``_result_array``).  Everything else -- uint16, smaller matrices, ``WIDEN_ON`` =
+    "device", no host library, bounce buffers that cannot be page-locked -- lands by DMA in the result's own type, in
+    page-locked memory from torch's caching host allocator (at most PROSSTT_AMD_PINNED_MAX_BYTES, default 32 GiB; beyond
+    that, or when page-locking fails, in ordinary memory); int64 is formed and uint16 narrowed on the device.
 
     row_order: the device matrix holds its cells in an order of PRESENTATION (``plan_order``): row i is cell
     ``row_order[i]``.  The host array comes back in plan order -- row ``row_order[i]`` = device row i -- the rows of every
-    chunk gathered on the device into the staging buffer that the conversion uses anyway (a gather of whole rows under
-    the transfer of the previous chunk: nothing is added to the PCIe-bound copy)."""
+    chunk gathered on the device under the transfer of the previous chunk: nothing is added to the PCIe-bound copy."""
     torch = _torch()
     dtype = np.dtype(dtype)
-    n, g = counts.shape
+    n, g = (int(v) for v in counts.shape)
     if dtype not in (np.dtype(np.int64), np.dtype(np.int32), np.dtype(np.uint16)):
         raise ValueError("host counts are int64, int32 or uint16")
     if n == 0 or g == 0:
         return np.zeros((n, g), dtype=dtype)
+    if dtype.itemsize == 2 and int(counts.max()) > 65535:
+        raise OverflowError("a count of %d does not fit uint16: ask for 'numpy32'" % int(counts.max()))
+    inv = _device_rows(row_order, n, counts.device)
+    own = {8: "i64", 4: "i32", 2: "u16"}[dtype.itemsize]
     if dtype.itemsize >= 4 and WIDEN_ON == "host" and n * g >= (1 << 24):
-        for wire in WIRES[WIRES.index(WIRE):] if WIRE in WIRES else WIRES[2:]:
-            if wire == "i32" and dtype.itemsize == 4:
-                break                                   # (int32 as it lies needs no widening: the copy below)
+        host = torch.from_numpy(_result_array((n, g), dtype))
+        for wire in (w for w in ("u8", "u16", "i32") if w != own):
             try:
-                return _to_host_widened(counts, chunk_bytes, row_order, dtype, wire)
+                _dense_attempt(counts, host, inv, chunk_bytes, wire)
+                return host.numpy()
             except _WireTooNarrow:
                 continue
-            except _NoBounceBuffers:
-                break                                   # (the device-widened copy below needs no page-locked memory)
-    # (torch has no arithmetic on uint16: the device narrows to int16 bit patterns, viewed as uint16 on the host)
-    t_dtype = {8: torch.int64, 4: torch.int32, 2: torch.int16}[dtype.itemsize]
-    host = None
-    if n * g * dtype.itemsize <= PINNED_RETURN_MAX:
-        try:
-            host = torch.empty((n, g), dtype=t_dtype, pin_memory=True)
-        except RuntimeError:
-            host = None
-    if host is None:
-        host = torch.empty((n, g), dtype=t_dtype)
-    rows = max(1, min(n, int(chunk_bytes) // (g * dtype.itemsize)))
-    dev = counts.device
-    compute = torch.cuda.current_stream(dev)
-    copier = torch.cuda.Stream(dev)
-    inv = None
-    if row_order is not None:
-        order = np.asarray(row_order, dtype=np.int64)
-        if order.shape != (n,):
-            raise ValueError("row_order must have one entry per row")
-        inv_host = np.empty(n, dtype=np.int64)
-        inv_host[order] = np.arange(n, dtype=np.int64)        # device row of host row j
-        inv = torch.as_tensor(inv_host).to(dev)
-    convert = t_dtype != torch.int32 or inv is not None
-    staging = [torch.empty((rows, g), dtype=t_dtype, device=dev) for _ in range(2 if rows < n else 1)] if convert else []
-    # (gathered rows of a chunk that is also widened or narrowed: ONE int32 scratch for the whole copy, not a fresh
-    # temporary per chunk beside a count matrix that may fill most of the device)
-    gathered = torch.empty((rows, g), dtype=torch.int32, device=dev) if (inv is not None and t_dtype != torch.int32) else None
-    copied = [None, None]
-    too_big = torch.zeros((), dtype=torch.int32, device=dev) if dtype.itemsize == 2 else None
-    for i, lo in enumerate(range(0, n, rows)):
-        hi = min(lo + rows, n)
-        if convert:
-            slot = i & 1
-            if copied[slot] is not None:
-                compute.wait_event(copied[slot])           # the buffer's previous chunk has left
-            stage = staging[slot][:hi - lo]
-            if too_big is not None:
-                too_big = torch.maximum(too_big, counts[lo:hi].max())
-            if inv is None:
-                stage.copy_(counts[lo:hi])                  # int32 -> int64, or the low 16 bits
-            elif t_dtype == torch.int32:
-                torch.index_select(counts, 0, inv[lo:hi], out=stage)
-            else:
-                torch.index_select(counts, 0, inv[lo:hi], out=gathered[:hi - lo])
-                stage.copy_(gathered[:hi - lo])
-        else:
-            stage = counts[lo:hi]
-        ready = torch.cuda.Event()
-        ready.record(compute)
-        copier.wait_event(ready)
-        with torch.cuda.stream(copier):
-            host[lo:hi].copy_(stage, non_blocking=True)
-            if convert:
-                copied[slot] = torch.cuda.Event()
-                copied[slot].record(copier)
-    copier.synchronize()
-    if too_big is not None and int(too_big) > 65535:
-        raise OverflowError("a count of %d does not fit uint16: ask for 'numpy32'" % int(too_big))
-    out = host.numpy()
-    return out.view(np.uint16) if dtype.itemsize == 2 else out
-
-
-# How an int64 / int32 host return of 2^24 counts or more travels.  WIDEN_ON = "host" (default): the matrix crosses PCIe in
-# a WIRE format narrower than its type and the host library's threads (libprosstt_amd_host.so) widen chunk i - 1 into the
-# result while chunk i is on the bus; "device": as rounds 2 to 5 did -- int64 formed on the device, 8 bytes per count over
-# PCIe, int32 copied as it lies (the choice for a host with very few cores).  WIRE = "u8" (default): the low 8 bits of
-# every count, 1 byte over PCIe, and beside them the entries that have higher bits set (two thirds of a count matrix are
-# zeros; one count in a thousand of C3 is above 255, the largest is 84 036) as (position, value) pairs that the pool writes
-# over the widened matrix at the end; a matrix in which more than one entry in 256 of a chunk is such an exception is sent
-# again with the next wider wire: "u16" (the low 16 bits), then "i32" (the int32 as it lies).  WIRE names the narrowest
-# wire that is tried.
-# (tools/host_widen_probe.py, tools/e2e_threads.py on an MI355X box's host: the pool writes 250 - 340 GB/s from eight threads
-# on; PCIe carries 52 GB/s.  C3 end to end: int64 147 -> 39 - 51 ms, int32 76 -> 32 - 39 ms, out="csr" 58 -> 38 ms.)
-WIDEN_ON = os.environ.get("PROSSTT_AMD_WIDEN", "host")
-WIRE = os.environ.get("PROSSTT_AMD_WIRE", "u8")
-WIRES = ("u8", "u16", "i32")
-RESULT_MEMORY = os.environ.get("PROSSTT_AMD_RESULT_MEMORY", "pageable")
-HOST_THREADS = int(os.environ.get("PROSSTT_AMD_HOST_THREADS", str(max(1, min(16, os.cpu_count() or 1)))))
-
-
-_result_blocks = []            # pageable result memory handed out before: [uint8 ndarray]; see _result_array
-_result_lock = threading.Lock()
-RESULT_CACHE_BYTES = int(os.environ.get("PROSSTT_AMD_RESULT_CACHE_BYTES", str(40 << 30)))
-
-
-def _result_array(shape, dtype):
-    """A pageable (n, g) result of the host-widened copy.  The memory is a numpy allocation (numpy asks for transparent
-    huge pages: the pool's first touch of 8 GB costs 45 ms instead of the 500 ms of 4 KB pages) that this module keeps a
-    reference to: once the caller has dropped the result and every view of it -- the block's reference count says so --
-    the next result of that size or less is laid over the same, already touched pages, as torch's caching host allocator
-    does for page-locked memory, without its 0.6 - 0.9 s of page-locking in front of the first 8 GB result."""
-    nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
-    with _result_lock:
-        block = cached = None
-        for i in range(len(_result_blocks)):
-            cached = _result_blocks[i]
-            # (references: the list's, this variable's, getrefcount's own argument)
-            if cached.size >= nbytes and cached.size <= 2 * nbytes + (1 << 20) and sys.getrefcount(cached) == 3:
-                block = _result_blocks.pop(i)
+            except _NoHostWidening:
                 break
-        del cached
-        if block is None:
-            block = np.empty(nbytes, dtype=np.uint8)
-        _result_blocks.append(block)
-        held = sum(b.size for b in _result_blocks)
-        while len(_result_blocks) > 1 and held > RESULT_CACHE_BYTES:
-            held -= _result_blocks.pop(0).size         # (the oldest; its memory goes when its last user does)
-    return block[:nbytes].view(dtype).reshape(shape)
+    # (torch has no arithmetic on uint16: the device narrows to int16 bit patterns, viewed as uint16 on the host)
+    host = _dma_result((n, g), {8: torch.int64, 4: torch.int32, 2: torch.int16}[dtype.itemsize])
+    _dense_attempt(counts, host, inv, chunk_bytes, own)
+    return host.numpy().view(dtype)
 
 
-def release_result_memory():
-    """Forget the recycled result blocks (PROSSTT_AMD_RESULT_CACHE_BYTES bounds what is kept: 40 GiB): the memory of the
-    ones nobody holds goes back to the system at once, the others' when their last user drops them."""
-    with _result_lock:
-        del _result_blocks[:]
-
-
-class _WireTooNarrow(Exception):
-    """Too many entries of a chunk do not fit the wire: the copy starts again with the next wider one."""
-
-
-class _NoBounceBuffers(Exception):
-    """The page-locked bounce buffers of the host-widened copy were refused."""
-
-
-def _to_host_widened(counts, chunk_bytes, row_order, dtype, wire):
-    """``to_host`` for int64 / int32 with the widening on the host: the chunks arrive in their wire format (int32 as the
-    device holds it, or narrowed to uint16 on the device) in two page-locked bounce buffers by asynchronous copies on a
-    second stream; chunk i - 1 is widened into the result by HOST_THREADS threads of the host library's pool
-    (libprosstt_amd_host.so, include/prosstt_amd_host.h: non-temporal AVX2 stores) while chunk i is on the bus.  The copy
-    is bound by the wire's 4 or 2 bytes per count over PCIe, not by the 8 or 4 of the result."""
+def _dense_attempt(counts, host, inv, chunk_bytes, wire):
+    """One try of ``to_host``: the device matrix over ``wire`` into the (n, g) host tensor ``host``, rows in host order
+    through ``inv``.  A wire narrower than ``host`` lands in page-locked bounce buffers, chunks of ``chunk_bytes`` of int32,
+    and the host library's threads widen it; the entries that "u8" / "u16" cannot carry travel beside it, at most one in
+    256 of a chunk (else _WireTooNarrow).  A wire as wide as ``host`` lands in it by DMA, chunks of ``chunk_bytes`` of it."""
     torch = _torch()
     n, g = (int(v) for v in counts.shape)
-    t_out = torch.int64 if dtype.itemsize == 8 else torch.int32
-    t_wire = {"u8": torch.uint8, "u16": torch.int16, "i32": torch.int32}[wire]     # (uint16 bit patterns: torch has no arithmetic on uint16)
-    high_bits = {"u8": -256, "u16": -65536, "i32": 0}[wire]
-    narrow = wire != "i32"
-    lib = _native.load_host()
-    widen = {("i32", 8): lib.prosstt_amd_host_widen_i32_i64, ("u16", 8): lib.prosstt_amd_host_widen_u16_i64,
-             ("u16", 4): lib.prosstt_amd_host_widen_u16_i32, ("u8", 8): lib.prosstt_amd_host_widen_u8_i64,
-             ("u8", 4): lib.prosstt_amd_host_widen_u8_i32}[(wire, dtype.itemsize)]
-    # The result is written by the host's threads, not by DMA: it needs no page-locking.  RESULT_MEMORY = "pageable"
-    # (default): numpy memory on transparent huge pages, recycled once the caller has dropped the result (_result_array) --
-    # C3 end to end: first call of a process 160 - 420 ms, then 40 - 50 ms; "pinned": from torch's caching host allocator --
-    # 0.5 to 0.9 s to page-lock C3's 8 GB the first time a size is asked for (first call 560 - 960 ms, then 54 - 80 ms;
-    # tools/hugepage_probe.py, tools/first_call.py).
-    host = None
-    if RESULT_MEMORY == "pinned" and n * g * dtype.itemsize <= PINNED_RETURN_MAX:
-        try:
-            host = torch.empty((n, g), dtype=t_out, pin_memory=True).numpy()
-        except RuntimeError:
-            host = None
-    if host is None:
-        host = _result_array((n, g), dtype)
-    rows = max(1, min(n, int(chunk_bytes) // (g * 4)))
     dev = counts.device
-    compute = torch.cuda.current_stream(dev)
-    copier = torch.cuda.Stream(dev)
-    inv = None
-    if row_order is not None:
-        order = np.asarray(row_order, dtype=np.int64)
-        if order.shape != (n,):
-            raise ValueError("row_order must have one entry per row")
-        inv_host = np.empty(n, dtype=np.int64)
-        inv_host[order] = np.arange(n, dtype=np.int64)        # device row of host row j
-        inv = torch.as_tensor(inv_host).to(dev)
-    slots = 2 if rows < n else 1
-    try:
-        bounce = [torch.empty((rows, g), dtype=t_wire, pin_memory=True) for _ in range(slots)]
-    except RuntimeError as exc:
-        raise _NoBounceBuffers() from exc
-    # device staging: the chunk's rows gathered (int32), and -- for the uint16 wire -- narrowed
-    gathered = torch.empty((rows, g), dtype=torch.int32, device=dev) if (inv is not None and narrow) else None
-    staged = [torch.empty((rows, g), dtype=t_wire, device=dev) for _ in range(slots)] if (inv is not None or narrow) else None
-    arrived = [None, None]
-    bounds = list(range(0, n, rows)) + [n]
-    host_at = host.ctypes.data
-    # A narrow wire: what did not fit travels beside the chunk as (position in the host matrix, value) pairs -- up to one
-    # entry in 256 of the chunk, in fixed-size buffers, so that nothing on the way waits for the device (the number of
-    # exceptions of a chunk is read when the chunk has arrived; more than fit: the copy starts again with a wider wire).
-    exceptions = []
-    room = max(1, rows * g // 256)
-    if narrow:
-        exc_where = [torch.empty(room, dtype=torch.int64, device=dev) for _ in range(slots)]
-        exc_value = [torch.empty(room, dtype=torch.int32, device=dev) for _ in range(slots)]
-        exc_count = [torch.empty((), dtype=torch.int64, device=dev) for _ in range(slots)]
-        try:
-            h_where = [torch.empty(room, dtype=torch.int64, pin_memory=True) for _ in range(slots)]
-            h_value = [torch.empty(room, dtype=torch.int32, pin_memory=True) for _ in range(slots)]
-            h_count = [torch.empty((), dtype=torch.int64, pin_memory=True) for _ in range(slots)]
-        except RuntimeError as exc:
-            raise _NoBounceBuffers() from exc
+    t_wire = getattr(torch, {"u8": "uint8", "u16": "int16", "i32": "int32", "i64": "int64"}[wire])
+    on_host = t_wire.itemsize < host.element_size()
+    rows = max(1, min(n, int(chunk_bytes) // (g * (4 if on_host else t_wire.itemsize))))
+    chunks = [(lo, min(lo + rows, n)) for lo in range(0, n, rows)]
+    slots = min(2, len(chunks))
+    if on_host:
+        widen = getattr(_host_lib(), "prosstt_amd_host_widen_%s_i%d" % (wire, 8 * host.element_size()))
+        bounce = [_bounce((rows, g), t_wire) for _ in range(slots)]
+    over = _Overflow(dev, slots, rows * g, 256, -256 if wire == "u8" else -65536) if on_host and wire != "i32" else None
+    # device staging: the chunk's rows gathered (int32; for the int32 wire straight into the slot) and converted to the wire
+    convert = wire != "i32"
+    staged = [torch.empty((rows, g), dtype=t_wire, device=dev) for _ in range(slots)] if (inv is not None or convert) else None
+    gathered = torch.empty((rows, g), dtype=torch.int32, device=dev) if (inv is not None and convert) else None
 
-    def note_exceptions(block, lo, slot):
-        """The entries of the chunk (int32, rows in host order from row ``lo``) with higher bits set, into the slot's buffers."""
-        flat = block.reshape(-1)
-        high = torch.bitwise_and(flat, high_bits)
-        exc_count[slot].copy_(torch.count_nonzero(high))
-        where = torch.nonzero_static(high, size=room, fill_value=0).squeeze(1)     # (padded with position 0: written with its own value)
-        torch.index_select(flat, 0, where, out=exc_value[slot])
-        torch.add(where, lo * g, out=exc_where[slot])
+    def stage(chunk, slot):
+        lo, hi = chunk
+        block = counts[lo:hi] if inv is None else torch.index_select(
+            counts, 0, inv[lo:hi], out=(gathered if convert else staged[slot])[:hi - lo])
+        if convert:
+            staged[slot][:hi - lo].copy_(block)              # int32 -> int64, or the low 16 / 8 bits
+        copies = [(bounce[slot][:hi - lo] if on_host else host[lo:hi], staged[slot][:hi - lo] if convert else block)]
+        return copies if over is None else copies + over.note(block.reshape(-1), lo * g, slot)
 
-    def widen_chunk(i):
-        lo, hi = bounds[i], bounds[i + 1]
-        slot = i % slots
-        arrived[slot].synchronize()
-        if narrow:
-            k = int(h_count[slot])
-            if k > room or k * 256 > (hi - lo) * g:
-                copier.synchronize()                    # (nothing of this attempt is in flight when its buffers go back)
-                torch.cuda.current_stream(dev).synchronize()
-                raise _WireTooNarrow()
-            if k:
-                exceptions.append((h_where[slot][:k].clone(), h_value[slot][:k].clone()))
-        if widen(ctypes.c_void_p(bounce[slot].data_ptr()), ctypes.c_void_p(host_at + lo * g * dtype.itemsize),
-                 ctypes.c_uint64((hi - lo) * g), HOST_THREADS) != 0:
-            raise RuntimeError("the host library refused its arguments")
+    def land(chunk, slot):
+        lo, hi = chunk
+        if over is not None:
+            over.take(slot, (hi - lo) * g)
+        _widen(widen, bounce[slot], host, lo * g, (hi - lo) * g)
 
-    copier.wait_stream(compute)                        # the matrix itself
-    for i in range(len(bounds) - 1):
-        lo, hi = bounds[i], bounds[i + 1]
-        slot = i % slots
-        if staged is None:
-            src = counts[lo:hi]
-        else:
-            if arrived[slot] is not None:
-                compute.wait_event(arrived[slot])       # the staging buffer's previous chunk has left
-            src = staged[slot][:hi - lo]
-            if inv is None:
-                src.copy_(counts[lo:hi])                # the low bits
-                note_exceptions(counts[lo:hi], lo, slot)
-            elif not narrow:
-                torch.index_select(counts, 0, inv[lo:hi], out=src)
-            else:
-                torch.index_select(counts, 0, inv[lo:hi], out=gathered[:hi - lo])
-                src.copy_(gathered[:hi - lo])
-                note_exceptions(gathered[:hi - lo], lo, slot)
-            ready = torch.cuda.Event()
-            ready.record(compute)
-            copier.wait_event(ready)
-        # (the bounce buffer's previous chunk, i - 2, was widened in the last turn of this loop)
-        with torch.cuda.stream(copier):
-            bounce[slot][:hi - lo].copy_(src, non_blocking=True)
-            if narrow:
-                h_count[slot].copy_(exc_count[slot], non_blocking=True)
-                h_where[slot].copy_(exc_where[slot], non_blocking=True)
-                h_value[slot].copy_(exc_value[slot], non_blocking=True)
-            arrived[slot] = torch.cuda.Event()
-            arrived[slot].record(copier)
-        if i >= 1:
-            widen_chunk(i - 1)
-    widen_chunk(len(bounds) - 2)
-    if exceptions:
-        where = np.ascontiguousarray(torch.cat([e[0] for e in exceptions]).numpy())
-        values = np.ascontiguousarray(torch.cat([e[1] for e in exceptions]).numpy())
-        if lib.prosstt_amd_host_scatter_i32(ctypes.c_void_p(host_at), dtype.itemsize, ctypes.c_void_p(where.ctypes.data),
-                                            ctypes.c_void_p(values.ctypes.data), ctypes.c_uint64(where.size), HOST_THREADS) != 0:
-            raise RuntimeError("the host library refused its arguments")
-    return host
+    _copy_chunks(dev, chunks, slots, stage, land if on_host else None)
+    if over is not None:
+        over.scatter(host)
 
 
-def to_host_csr(counts, chunk_bytes=256 << 20, row_order=None, _narrow=(True, True)):
+def to_host_csr(counts, chunk_bytes=256 << 20, row_order=None):
     """int32 device counts -> ``scipy.sparse.csr_matrix`` (int32 data, int32 column indices sorted within a row, int64
     row pointers) in plan order: what the single-cell toolchains downstream of the reference's count files hold a count
     matrix in.  Two thirds of such a matrix are zeros, and only the NON-ZEROS cross PCIe -- 3 bytes each (the value's low 8
-    bits, a 16-bit column index; 8 bytes for a matrix of large counts or of more than 65 536 columns), widened by the host
+    bits, a 16-bit column index; more for a matrix of large counts or of more than 65 536 columns), widened by the host
     library's threads -- and the dense matrix never exists on the host.
 
     Two passes over the device matrix, a chunk of rows at a time: the non-zeros per row first (the row pointers, and with
-    them the exact size of the page-locked result), then every chunk's non-zeros are compacted on the device (row-major:
-    rows ascending, columns ascending within a row) into one of two staging pairs and copied on a second stream straight
-    into their final place while the next chunk is compacted.  ``row_order``: as in ``to_host`` (device row i is cell
-    ``row_order[i]``; the gather of whole rows rides in the first step of each chunk)."""
+    them the exact size of the result), then every chunk's non-zeros are compacted on the device (row-major) and copied
+    toward their final place while the next chunk is compacted (``_csr_attempt``).  ``row_order``: as in ``to_host``
+    (device row i is cell ``row_order[i]``; the gather of whole rows rides in the first step of each chunk)."""
     torch = _torch()
     import scipy.sparse as sparse
     n, g = (int(v) for v in counts.shape)
@@ -689,165 +487,269 @@ def to_host_csr(counts, chunk_bytes=256 << 20, row_order=None, _narrow=(True, Tr
         raise ValueError("column indices are int32")
     dev = counts.device
     rows = max(1, min(n, int(chunk_bytes) // (g * 4)))
-    inv = None
-    if row_order is not None:
-        order = np.asarray(row_order, dtype=np.int64)
-        if order.shape != (n,):
-            raise ValueError("row_order must have one entry per row")
-        inv_host = np.empty(n, dtype=np.int64)
-        inv_host[order] = np.arange(n, dtype=np.int64)        # device row of host row j
-        inv = torch.as_tensor(inv_host).to(dev)
+    bounds = [(lo, min(lo + rows, n)) for lo in range(0, n, rows)]
+    inv = _device_rows(row_order, n, dev)
     # pass 1: non-zeros of every row, in the order of the rows on the host
     per_row = torch.empty(n, dtype=torch.int64, device=dev)
-    for lo in range(0, n, rows):
-        hi = min(lo + rows, n)
+    for lo, hi in bounds:
         per_row[lo:hi] = torch.count_nonzero(counts[lo:hi], dim=1)
     if inv is not None:
         per_row = per_row.index_select(0, inv)
     indptr = np.zeros(n + 1, dtype=np.int64)
     np.cumsum(per_row.cpu().numpy(), out=indptr[1:])
     total = int(indptr[-1])
-    bounds = list(range(0, n, rows)) + [n]
-    cap = max(int(indptr[b] - indptr[a]) for a, b in zip(bounds[:-1], bounds[1:]))
+    # pass 2, over the chunks that hold non-zeros: (rows lo:hi, their non-zeros first:last)
+    chunks = [(lo, hi, int(indptr[lo]), int(indptr[hi])) for lo, hi in bounds if indptr[hi] > indptr[lo]]
+    made = {}
 
-    def host_array(written_by_the_host):
-        """A result array as a torch tensor: page-locked when DMA lands in it (or RESULT_MEMORY says so), else over a
-        recycled pageable block (_result_array)."""
-        if written_by_the_host and RESULT_MEMORY != "pinned":
-            return torch.from_numpy(_result_array((total,), np.int32))
-        if 0 < total * 4 <= PINNED_RETURN_MAX:
+    def attempt(vals, cols):
+        for name, wire in (("data", vals), ("indices", cols)):      # each result array once per call and kind of memory
+            if (name, wire) not in made:
+                made[name, wire] = (_dma_result((total,), torch.int32) if wire == "i32"
+                                    else torch.from_numpy(_result_array((total,), np.int32)))
+        data, indices = made["data", vals], made["indices", cols]
+        _csr_attempt(counts, inv, rows, chunks, data, indices, vals, cols)
+        out = sparse.csr_matrix((data.numpy(), indices.numpy(), indptr), shape=(n, g), copy=False)
+        out.has_sorted_indices = True
+        return out
+
+    if WIDEN_ON == "host" and total >= (1 << 22):
+        cols = "u16" if g <= 65536 else "i32"
+        for vals in ("u8", "i32"):
             try:
-                return torch.empty(total, dtype=torch.int32, pin_memory=True)
-            except RuntimeError:
-                pass
-        return torch.empty(total, dtype=torch.int32)
+                return attempt(vals, cols)
+            except _WireTooNarrow:
+                continue
+            except _NoHostWidening:
+                break
+    return attempt("i32", "i32")
 
+
+def _csr_attempt(counts, inv, rows, chunks, data, indices, vals_wire, cols_wire):
+    """Pass 2 of ``to_host_csr`` over one wire configuration: the non-zeros of every chunk (lo, hi, first, last) compacted
+    on the device, values over ``vals_wire`` into ``data[first:last]``, column indices over ``cols_wire`` into
+    ``indices[first:last]``.  "u8" values (those above 255 beside them, at most one in 16 of a chunk's, else
+    _WireTooNarrow) and "u16" columns land in page-locked bounce buffers for the host library's threads; "i32" by DMA."""
+    torch = _torch()
+    g = int(counts.shape[1])
+    dev = counts.device
+    cap = max((last - first for _, _, first, last in chunks), default=0)
+    slots = min(2, len(chunks))
+    lib = _host_lib() if (vals_wire, cols_wire) != ("i32", "i32") else None
+    bounce_v = [_bounce(cap, torch.uint8) for _ in range(slots)] if vals_wire == "u8" else None
+    bounce_c = [_bounce(cap, torch.int16) for _ in range(slots)] if cols_wire == "u16" else None
+    over = _Overflow(dev, slots, cap, 16, -256) if vals_wire == "u8" else None
+    vals = [torch.empty(cap, dtype=torch.uint8 if vals_wire == "u8" else torch.int32, device=dev) for _ in range(slots)]
+    cols = [torch.empty(cap, dtype=torch.int16 if cols_wire == "u16" else torch.int32, device=dev) for _ in range(slots)]
+    vals32 = torch.empty(cap, dtype=torch.int32, device=dev) if over is not None else None
+    gathered = torch.empty((rows, g), dtype=torch.int32, device=dev) if inv is not None else None
+
+    def stage(chunk, slot):
+        lo, hi, first, last = chunk
+        k = last - first
+        block = counts[lo:hi] if inv is None else torch.index_select(counts, 0, inv[lo:hi], out=gathered[:hi - lo])
+        flat = block.reshape(-1)
+        where = torch.nonzero_static(flat, size=k, fill_value=0).squeeze(1)     # ascending flat positions = CSR order
+        if over is None:
+            torch.index_select(flat, 0, where, out=vals[slot][:k])
+        else:
+            torch.index_select(flat, 0, where, out=vals32[:k])
+            vals[slot][:k].copy_(vals32[:k])                    # the low 8 bits
+        cols[slot][:k].copy_(torch.remainder(where, g))
+        copies = [(data[first:last] if bounce_v is None else bounce_v[slot][:k], vals[slot][:k]),
+                  (indices[first:last] if bounce_c is None else bounce_c[slot][:k], cols[slot][:k])]
+        return copies if over is None else copies + over.note(vals32[:k], first, slot)
+
+    def land(chunk, slot):
+        first, last = chunk[2:]
+        if bounce_v is not None:
+            over.take(slot, last - first)
+            _widen(lib.prosstt_amd_host_widen_u8_i32, bounce_v[slot], data, first, last - first)
+        if bounce_c is not None:
+            _widen(lib.prosstt_amd_host_widen_u16_i32, bounce_c[slot], indices, first, last - first)
+
+    _copy_chunks(dev, chunks, slots, stage, land if lib is not None else None)
+    if over is not None:
+        over.scatter(data)
+
+
+def _copy_chunks(dev, chunks, slots, stage, land=None):
+    """The double-buffered copy of a device matrix to the host, a chunk at a time, on a second stream; chunk i uses the
+    buffers of slot i % ``slots``.  ``stage(chunk, slot)`` enqueues on the current stream what the chunk sends and returns
+    its copies, (host destination, device source) pairs; ``land(chunk, slot)`` finishes the chunk on the host once they
+    have arrived.  The current stream stages into a slot only once the slot's previous chunk has left; the copier starts
+    on a chunk once it is staged; chunk i - 1 lands while chunk i is on the bus, so a slot's previous chunk has landed
+    before its bounce buffers are written again.  Nothing is in flight when this returns or raises."""
+    torch = _torch()
     compute = torch.cuda.current_stream(dev)
     copier = torch.cuda.Stream(dev)
-    slots = 2 if len(bounds) > 2 else 1
-    gathered = torch.empty((rows, g), dtype=torch.int32, device=dev) if inv is not None else None
-    # The wire (as in ``to_host``): values as their low 8 bits -- the few above 255 beside them as (position, value) pairs --
-    # and column indices as 16 bits when the matrix has at most 65 536 columns: 3 bytes per non-zero over PCIe instead of
-    # 8, widened into the two int32 arrays by the host library's threads under the transfer of the next chunk.
-    # (_narrow: which of the two this attempt may narrow -- the call starts again without the first for a matrix of large
-    # counts, without both when the page-locked bounce buffers are refused)
-    narrow_vals = _narrow[0] and WIDEN_ON == "host" and WIRE == "u8" and total >= (1 << 22)
-    narrow_cols = _narrow[1] and WIDEN_ON == "host" and WIRE in ("u8", "u16") and total >= (1 << 22) and g <= 65536
-    lib = _native.load_host() if (narrow_vals or narrow_cols) else None
-    data, indices = host_array(narrow_vals), host_array(narrow_cols)
-    t_vals = torch.uint8 if narrow_vals else torch.int32
-    t_cols = torch.int16 if narrow_cols else torch.int32
-    vals = [torch.empty(max(cap, 1), dtype=t_vals, device=dev) for _ in range(slots)]
-    cols = [torch.empty(max(cap, 1), dtype=t_cols, device=dev) for _ in range(slots)]
-    vals32 = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if narrow_vals else None
+    arrived = [None] * slots
     try:
-        bounce_v = [torch.empty(max(cap, 1), dtype=t_vals, pin_memory=True) for _ in range(slots)] if narrow_vals else None
-        bounce_c = [torch.empty(max(cap, 1), dtype=t_cols, pin_memory=True) for _ in range(slots)] if narrow_cols else None
-    except RuntimeError:
-        return to_host_csr(counts, chunk_bytes, row_order, _narrow=(False, False))
-    copied = [None, None]
-    spans = [None, None]
-    exceptions = []
-    # (the values above 255 of a chunk: in fixed-size buffers beside it, their number read when the chunk has arrived --
-    # as in ``_to_host_widened``; more than one in sixteen: 4-byte values after all)
-    room = max(1, cap // 16)
-    if narrow_vals:
-        exc_where = [torch.empty(room, dtype=torch.int64, device=dev) for _ in range(slots)]
-        exc_value = [torch.empty(room, dtype=torch.int32, device=dev) for _ in range(slots)]
-        exc_count = [torch.empty((), dtype=torch.int64, device=dev) for _ in range(slots)]
-        try:
-            h_where = [torch.empty(room, dtype=torch.int64, pin_memory=True) for _ in range(slots)]
-            h_value = [torch.empty(room, dtype=torch.int32, pin_memory=True) for _ in range(slots)]
-            h_count = [torch.empty((), dtype=torch.int64, pin_memory=True) for _ in range(slots)]
-        except RuntimeError:
-            return to_host_csr(counts, chunk_bytes, row_order, _narrow=(False, False))
-
-    class _LargeCounts(Exception):
-        pass
-
-    def widen_chunk(slot):
-        """The narrow halves of the chunk in ``slot``: wait for them, widen them into their place."""
-        if spans[slot] is None:
-            return
-        first, last = spans[slot]
-        spans[slot] = None
-        copied[slot].synchronize()
-        k = last - first
-        if narrow_vals:
-            n_big = int(h_count[slot])
-            if n_big > room or n_big * 16 > k:
-                raise _LargeCounts()
-            if n_big:
-                exceptions.append((h_where[slot][:n_big].clone(), h_value[slot][:n_big].clone()))
-        if narrow_vals and lib.prosstt_amd_host_widen_u8_i32(ctypes.c_void_p(bounce_v[slot].data_ptr()), ctypes.c_void_p(data.data_ptr() + 4 * first),
-                                                             ctypes.c_uint64(k), HOST_THREADS) != 0:
-            raise RuntimeError("the host library refused its arguments")
-        if narrow_cols and lib.prosstt_amd_host_widen_u16_i32(ctypes.c_void_p(bounce_c[slot].data_ptr()), ctypes.c_void_p(indices.data_ptr() + 4 * first),
-                                                              ctypes.c_uint64(k), HOST_THREADS) != 0:
-            raise RuntimeError("the host library refused its arguments")
-
-    # pass 2 (the number of non-zeros of every chunk is known from pass 1: torch.nonzero_static, no waiting for the device)
-    def pass_two():
-        for i, (lo, hi) in enumerate(zip(bounds[:-1], bounds[1:])):
-            first, last = int(indptr[lo]), int(indptr[hi])
-            k = last - first
-            if k == 0:
-                continue
+        for i, chunk in enumerate(chunks):
             slot = i % slots
-            if copied[slot] is not None:
-                compute.wait_event(copied[slot])               # the staging pair's previous chunk has left
-            if inv is None:
-                block = counts[lo:hi]
-            else:
-                block = torch.index_select(counts, 0, inv[lo:hi], out=gathered[:hi - lo])
-            flat = block.reshape(-1)
-            where = torch.nonzero_static(flat, size=k, fill_value=0).squeeze(1)     # ascending flat positions = CSR order
-            if narrow_vals:
-                torch.index_select(flat, 0, where, out=vals32[:k])
-                vals[slot][:k].copy_(vals32[:k])                # the low 8 bits
-                high = torch.bitwise_and(vals32[:k], -256)
-                exc_count[slot].copy_(torch.count_nonzero(high))
-                big = torch.nonzero_static(high, size=room, fill_value=0).squeeze(1)
-                torch.index_select(vals32[:k], 0, big, out=exc_value[slot])
-                torch.add(big, first, out=exc_where[slot])
-            else:
-                torch.index_select(flat, 0, where, out=vals[slot][:k])
-            cols[slot][:k].copy_(torch.remainder(where, g))
-            del where
-            widen_chunk(slot)                                  # (the bounce buffers' previous chunk, i - 2)
-            ready = torch.cuda.Event()
-            ready.record(compute)
-            copier.wait_event(ready)
+            if arrived[slot] is not None:
+                compute.wait_event(arrived[slot])           # the slot's previous chunk has left
+            copies = stage(chunk, slot)
+            copier.wait_stream(compute)
             with torch.cuda.stream(copier):
-                (bounce_v[slot][:k] if narrow_vals else data[first:last]).copy_(vals[slot][:k], non_blocking=True)
-                (bounce_c[slot][:k] if narrow_cols else indices[first:last]).copy_(cols[slot][:k], non_blocking=True)
-                if narrow_vals:
-                    h_count[slot].copy_(exc_count[slot], non_blocking=True)
-                    h_where[slot].copy_(exc_where[slot], non_blocking=True)
-                    h_value[slot].copy_(exc_value[slot], non_blocking=True)
-                copied[slot] = torch.cuda.Event()
-                copied[slot].record(copier)
-            spans[slot] = (first, last)
-            if slots == 2:
-                widen_chunk(slot ^ 1)                          # chunk i - 1, while chunk i is on the bus
+                for dst, src in copies:
+                    dst.copy_(src, non_blocking=True)
+                arrived[slot] = copier.record_event()
+            if land is not None and i >= 1:
+                arrived[(i - 1) % slots].synchronize()
+                land(chunks[i - 1], (i - 1) % slots)
         copier.synchronize()
-        for slot in range(slots):
-            widen_chunk(slot)
-    try:
-        pass_two()
-    except _LargeCounts:                                   # a matrix of large counts: 4-byte values after all
-        copier.synchronize()
+        if land is not None and chunks:
+            land(chunks[-1], (len(chunks) - 1) % slots)
+    except BaseException:
+        copier.synchronize()                                # (nothing of this attempt is in flight when its buffers go back)
         compute.synchronize()
-        return to_host_csr(counts, chunk_bytes, row_order, _narrow=(False, _narrow[1]))
-    if exceptions:
-        where = np.ascontiguousarray(torch.cat([e[0] for e in exceptions]).numpy())
-        values = np.ascontiguousarray(torch.cat([e[1] for e in exceptions]).numpy())
-        if lib.prosstt_amd_host_scatter_i32(ctypes.c_void_p(data.data_ptr()), 4, ctypes.c_void_p(where.ctypes.data),
-                                            ctypes.c_void_p(values.ctypes.data), ctypes.c_uint64(where.size), HOST_THREADS) != 0:
-            raise RuntimeError("the host library refused its arguments")
-    out = sparse.csr_matrix((data.numpy(), indices.numpy(), indptr), shape=(n, g), copy=False)
-    out.has_sorted_indices = True
-    return out
+        raise
+
+
+class _Overflow:
+    """The side channel of a narrow wire: the entries of a chunk with a bit of ``mask`` set (higher bits than the wire
+    carries, or a negative count) travel beside it as (position in the result, value) pairs, in fixed-size buffers of
+    each slot with room for one entry in ``per`` of ``capacity``, so that nothing on the way waits for the device; more
+    than one in ``per`` of a chunk, counted when it has landed, is _WireTooNarrow.  The pairs are written at the end."""
+
+    def __init__(self, dev, slots, capacity, per, mask):
+        torch = _torch()
+        self.room, self.per, self.mask = max(1, capacity // per), per, mask
+        # per slot: (positions, values, their number) on the device, and page-locked on the host
+        self.dev = [tuple(torch.empty(shape, dtype=t, device=dev) for shape, t in
+                          ((self.room, torch.int64), (self.room, torch.int32), ((), torch.int64))) for _ in range(slots)]
+        self.host = [tuple(_bounce(t.shape, t.dtype) for t in bufs) for bufs in self.dev]
+        self.pairs = []
+
+    def note(self, values, offset, slot):
+        """Stage the entries of the flat int32 device tensor ``values`` beyond the wire, at ``offset`` + their index."""
+        torch = _torch()
+        where, value, count = self.dev[slot]
+        high = torch.bitwise_and(values, self.mask)
+        count.copy_(torch.count_nonzero(high))
+        at = torch.nonzero_static(high, size=self.room, fill_value=0).squeeze(1)     # (padded with index 0: never read)
+        torch.index_select(values, 0, at, out=value)
+        torch.add(at, offset, out=where)
+        return list(zip(self.host[slot], self.dev[slot]))
+
+    def take(self, slot, size):
+        """Keep the pairs of the chunk of ``size`` entries that has landed in ``slot``."""
+        where, value, count = self.host[slot]
+        k = int(count)
+        if k > self.room or k * self.per > size:
+            raise _WireTooNarrow()
+        if k:
+            self.pairs.append((where[:k].clone(), value[:k].clone()))
+
+    def scatter(self, result):
+        """Write the pairs over the widened int32 / int64 host tensor ``result``."""
+        if self.pairs:
+            torch = _torch()
+            where, values = (torch.cat([pair[i] for pair in self.pairs]) for i in (0, 1))
+            if _native.load_host().prosstt_amd_host_scatter_i32(result.data_ptr(), result.element_size(), where.data_ptr(),
+                                                               values.data_ptr(), where.numel(), HOST_THREADS) != 0:
+                raise RuntimeError("the host library refused its arguments")
+
+
+class _WireTooNarrow(Exception):
+    """Too many entries of a chunk do not fit the wire: the copy starts again with the next wider one."""
+
+
+class _NoHostWidening(Exception):
+    """No host library or no page-locked bounce buffers: the copy falls through to the one in the result's own type."""
+
+
+_warned_no_host_lib = False
+
+
+def _host_lib():
+    """libprosstt_amd_host.so, or _NoHostWidening (and, the first time in the process, a RuntimeWarning)."""
+    global _warned_no_host_lib
+    try:
+        return _native.load_host()
+    except RuntimeError as exc:
+        if not _warned_no_host_lib:
+            _warned_no_host_lib = True
+            warnings.warn("%s: host returns are not widened on the host" % exc, RuntimeWarning)
+        raise _NoHostWidening() from exc
+
+
+def _bounce(shape, t_dtype):
+    """A page-locked host buffer that a narrow wire lands in, or _NoHostWidening."""
+    try:
+        return _torch().empty(shape, dtype=t_dtype, pin_memory=True)
+    except RuntimeError as exc:
+        raise _NoHostWidening() from exc
+
+
+def _widen(fn, src, dst, first, count):
+    """The host library's widening ``fn`` of ``count`` entries of ``src`` into the host tensor ``dst`` from entry ``first``."""
+    if fn(src.data_ptr(), dst.data_ptr() + first * dst.element_size(), count, HOST_THREADS) != 0:
+        raise RuntimeError("the host library refused its arguments")
+
+
+def _dma_result(shape, t_dtype):
+    """A host tensor that DMA lands a result in: page-locked up to PINNED_RETURN_MAX bytes, else ordinary memory."""
+    torch = _torch()
+    if 0 < int(np.prod(shape)) * t_dtype.itemsize <= PINNED_RETURN_MAX:
+        try:
+            return torch.empty(shape, dtype=t_dtype, pin_memory=True)
+        except RuntimeError:
+            pass
+    return torch.empty(shape, dtype=t_dtype)
+
+
+def _device_rows(row_order, n, dev):
+    """The device row of every host row (the inverse of ``row_order``) as an int64 device tensor; None without an order."""
+    if row_order is None:
+        return None
+    order = np.asarray(row_order, dtype=np.int64)
+    if order.shape != (n,):
+        raise ValueError("row_order must have one entry per row")
+    inv = np.empty(n, dtype=np.int64)
+    inv[order] = np.arange(n, dtype=np.int64)
+    return _torch().as_tensor(inv).to(dev)
+
+
+_free_blocks = []              # pageable result memory that no result holds, oldest first; see _result_array
+_result_lock = threading.Lock()
+RESULT_CACHE_BYTES = int(os.environ.get("PROSSTT_AMD_RESULT_CACHE_BYTES", str(40 << 30)))
+
+
+class _Lease:
+    """A result's hold on its block: the result is ``np.asarray(lease)``, so every numpy view and torch tensor of it keeps
+    the lease alive, and the block goes back to the free blocks when the last of them goes."""
+    __slots__ = ("__array_interface__", "__weakref__")
+
+    def __init__(self, block, shape, dtype):
+        self.__array_interface__ = dict(shape=tuple(shape), typestr=np.dtype(dtype).str, data=(block.ctypes.data, False),
+                                        version=3)
+
+
+def _result_array(shape, dtype):
+    """A pageable result that the host library's threads write, on a numpy allocation (numpy asks for transparent huge
+    pages: the first touch of 8 GB costs 45 ms instead of the 500 ms of 4 KB pages) lent to it: once the result and every
+    view of it -- numpy or torch -- are gone, the next result of that size or a little less is laid over the same, already
+    touched pages, without the 0.6 - 0.9 s of page-locking that torch's caching host allocator puts before 8 GB."""
+    nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
+    with _result_lock:
+        fits = [i for i, free in enumerate(_free_blocks) if nbytes <= free.size <= 2 * nbytes + (1 << 20)]
+        block = _free_blocks.pop(fits[0]) if fits else np.empty(nbytes, dtype=np.uint8)
+        held = sum(free.size for free in _free_blocks)
+        while _free_blocks and held > RESULT_CACHE_BYTES:
+            held -= _free_blocks.pop(0).size             # the oldest first
+    lease = _Lease(block, shape, dtype)
+    # (a plain append, no lock: the finalizer may run in any thread, in a collection while _result_lock is held)
+    weakref.finalize(lease, _free_blocks.append, block)
+    return np.asarray(lease)
+
+
+def release_result_memory():
+    """Free the recycled result blocks that no result holds (PROSSTT_AMD_RESULT_CACHE_BYTES bounds them: 40 GiB); a block
+    that a result still holds joins them when its last user drops it."""
+    with _result_lock:
+        del _free_blocks[:]
 
 
 HOST_OUTS = tuple(HOST_DTYPES) + ("csr",)
@@ -956,11 +858,6 @@ class PresentedCounts:
 
     def to_host(self, out="numpy"):
         return host_return(self.counts, out, row_order=self.cell_of_row)
-
-
-def to_host_int64(counts, chunk_bytes=256 << 20):
-    """int32 device counts -> the reference's int64 ndarray (simulation.py:651); see ``to_host``."""
-    return to_host(counts, np.int64, chunk_bytes)
 
 
 _contexts = {}

@@ -259,13 +259,13 @@ def test_compact_host_returns_and_chunk_generator():
             pass
 
 
-def test_host_returns_widened_on_the_host_equal_the_device_widened_ones(monkeypatch):
+def test_dense_host_returns_over_each_wire_equal_the_device_widened_ones(monkeypatch):
     """int64 / int32 returns of 2^24 counts and more cross PCIe in a wire format (the low 8 bits of every count and, beside
     them, the entries that have higher bits set; the low 16 bits, then int32, when there are too many of those) and are
     widened by the host library's threads under the next chunk's transfer == widened on the device
     (PROSSTT_AMD_WIDEN=device) == the device tensor: with and without the row gather, for one chunk, many chunks and a
     ragged last chunk, for matrices that fit each wire with a few exceptions (counts above it, negative entries) and one
-    that fits none."""
+    that fits none; without the host library, a RuntimeWarning and the copy in the result's own type."""
     import torch
     from prosstt_amd import device
     gen = torch.Generator(device="cuda").manual_seed(5)
@@ -283,11 +283,11 @@ def test_host_returns_widened_on_the_host_equal_the_device_widened_ones(monkeypa
     medium = with_exceptions(torch.randint(0, 65536, (n, g), device="cuda", generator=gen, dtype=torch.int32), 70000)
     large = torch.randint(0, 65536, (n, g), device="cuda", generator=gen, dtype=torch.int32) + 100000
     calls = []
-    real = device._to_host_widened
-    monkeypatch.setattr(device, "_to_host_widened", lambda *a: (calls.append(a[4]), real(*a))[1])
+    real = device._dense_attempt
+    monkeypatch.setattr(device, "_dense_attempt", lambda *a: (calls.append(a[4]), real(*a))[1])
     for name, counts, wires in (("small", small, ["u8"]), ("medium", medium, ["u8", "u16"]), ("large", large, ["u8", "u16", "i32"])):
         want32 = counts.cpu().numpy()
-        for dtype in (np.int64, np.int32):
+        for dtype, own in ((np.int64, "i64"), (np.int32, "i32")):
             want = want32.astype(dtype)
             want_perm = np.empty_like(want)
             want_perm[order] = want
@@ -297,29 +297,38 @@ def test_host_returns_widened_on_the_host_equal_the_device_widened_ones(monkeypa
                     del calls[:]
                     got = device.to_host(counts, dtype, chunk_bytes=chunk_bytes)
                     assert got.dtype == dtype and np.array_equal(got, want), (name, dtype, where, chunk_bytes)
-                    if where == "host":                 # (int32 of a matrix no narrow wire can carry: copied as it lies)
-                        assert calls == [w for w in wires if not (w == "i32" and dtype == np.int32)], (name, dtype, calls)
+                    # (the wires tried; for int32 the "i32" wire is the plain copy in the result's own type)
+                    assert calls == (wires if where == "host" else [own]), (name, dtype, calls)
                     got = device.to_host(counts, dtype, chunk_bytes=chunk_bytes, row_order=order)
                     assert np.array_equal(got, want_perm), (name, dtype, where, chunk_bytes)
     monkeypatch.setattr(device, "WIDEN_ON", "host")
-    for narrowest, tried in (("i32", ["i32"]), ("u16", ["u16"])):
-        monkeypatch.setattr(device, "WIRE", narrowest)
-        del calls[:]
-        assert np.array_equal(device.to_host(medium, np.int64, chunk_bytes=4 * g * 777), medium.cpu().numpy().astype(np.int64)) and calls == tried
-    monkeypatch.setattr(device, "WIRE", "u8")
     monkeypatch.setattr(device, "HOST_THREADS", 3)
     assert np.array_equal(device.to_host(small, np.int64, chunk_bytes=4 * g * 777, row_order=order)[order], small.cpu().numpy())
-    # the result in ordinary memory (a numpy array; PROSSTT_AMD_RESULT_MEMORY=pageable) instead of page-locked memory
-    monkeypatch.setattr(device, "RESULT_MEMORY", "pageable")
+    # the result in ordinary memory (a numpy array lent by _result_array) instead of page-locked memory
     for dtype in (np.int64, np.int32):
         got = device.to_host(small, dtype, chunk_bytes=4 * g * 500, row_order=order)
         assert got.dtype == dtype and got.flags.writeable and np.array_equal(got[order], small.cpu().numpy())
+        assert not torch.from_numpy(got).is_pinned()
+
+    def no_host_library():
+        raise RuntimeError("libprosstt_amd_host.so not found")
+    monkeypatch.setattr(device._native, "load_host", no_host_library)
+    monkeypatch.setattr(device, "_warned_no_host_lib", False)
+    with pytest.warns(RuntimeWarning):
+        for dtype, own in ((np.int64, "i64"), (np.int32, "i32")):
+            for row_order in (None, order):
+                del calls[:]
+                got = device.to_host(small, dtype, chunk_bytes=4 * g * 500, row_order=row_order)
+                got = got if row_order is None else got[order]
+                assert got.dtype == dtype and np.array_equal(got, small.cpu().numpy()) and calls == ["u8", own], (dtype, calls)
 
 
-def test_sparse_return_over_the_narrow_wire(monkeypatch):
+def test_sparse_return_over_each_wire_configuration(monkeypatch):
     """to_host_csr of a matrix with 2^22 non-zeros and more: values as their low 8 bits (+ the larger ones as pairs), column
     indices as 16 bits, widened by the host library == the dense matrix; a matrix of large counts falls back to 4-byte
-    values; WIRE / WIDEN_ON switch the narrowing off; rows in plan order through row_order."""
+    values; WIDEN_ON = "device" and a missing host library (with a RuntimeWarning) switch the narrowing off; rows in plan
+    order through row_order."""
+    import contextlib
     import scipy.sparse as sparse
     import torch
     from prosstt_amd import device
@@ -331,20 +340,33 @@ def test_sparse_return_over_the_narrow_wire(monkeypatch):
     small[9, :64] = 70000
     large = (torch.randint(300, 100000, (n, g), device="cuda", generator=gen, dtype=torch.int32)) * keep
     order = np.random.default_rng(2).permutation(n)
+    calls = []
+    real = device._csr_attempt
+    monkeypatch.setattr(device, "_csr_attempt", lambda *a: (calls.append(a[6:]), real(*a))[1])
+
+    def no_host_library():
+        raise RuntimeError("libprosstt_amd_host.so not found")
     for name, counts in (("small", small), ("large", large)):
         want = counts.cpu().numpy()
         assert np.count_nonzero(want) >= 1 << 22
         want_perm = np.empty_like(want)
         want_perm[order] = want
-        for wire, where in (("u8", "host"), ("u16", "host"), ("i32", "host"), ("u8", "device")):
-            monkeypatch.setattr(device, "WIRE", wire)
-            monkeypatch.setattr(device, "WIDEN_ON", where)
-            for chunk_bytes in (256 << 20, 4 * g * 1000, 4 * g * 333):
-                S = device.to_host_csr(counts, chunk_bytes=chunk_bytes)
-                assert sparse.isspmatrix_csr(S) and S.dtype == np.int32 and S.indices.dtype == np.int32 and S.has_sorted_indices
-                assert S.nnz == np.count_nonzero(want) and np.array_equal(S.toarray(), want), (name, wire, where, chunk_bytes)
-            S = device.to_host_csr(counts, chunk_bytes=4 * g * 777, row_order=order)
-            assert np.array_equal(S.toarray(), want_perm), (name, wire, where)
+        narrow = [("u8", "u16")] if name == "small" else [("u8", "u16"), ("i32", "u16")]
+        for case, tried in (("host", narrow), ("device", [("i32", "i32")]), ("no host library", [("u8", "u16"), ("i32", "i32")])):
+            with monkeypatch.context() as m:
+                m.setattr(device, "WIDEN_ON", "device" if case == "device" else "host")
+                if case == "no host library":
+                    m.setattr(device._native, "load_host", no_host_library)
+                    m.setattr(device, "_warned_no_host_lib", False)
+                with pytest.warns(RuntimeWarning) if case == "no host library" else contextlib.nullcontext():
+                    for chunk_bytes, row_order in ((256 << 20, None), (4 * g * 1000, None), (4 * g * 333, None),
+                                                   (4 * g * 777, order)):
+                        del calls[:]
+                        S = device.to_host_csr(counts, chunk_bytes=chunk_bytes, row_order=row_order)
+                        assert sparse.isspmatrix_csr(S) and S.dtype == np.int32 and S.indices.dtype == np.int32
+                        assert S.has_sorted_indices
+                        assert S.nnz == np.count_nonzero(want) and calls == tried, (name, case, chunk_bytes, calls)
+                        assert np.array_equal(S.toarray(), want if row_order is None else want_perm), (name, case, chunk_bytes)
 
 
 def test_max_attempts_guard():

@@ -420,14 +420,28 @@ def test_plan_order_is_a_stable_grouping_by_row():
         device.plan_order(np.array([0, 9], np.int32), 9)
 
 
-def test_pageable_result_blocks_are_recycled_only_when_nobody_holds_them():
-    """device._result_array (the pageable results of the host-widened copy): a block is laid under a new result only
-    once the earlier result and every view of it -- numpy or torch -- are gone; a small result never takes a huge
-    block; the cache forgets its oldest blocks beyond its budget."""
+def test_leased_result_blocks_are_recycled_only_when_nobody_holds_them(monkeypatch):
+    """device._result_array (the pageable results of the host-widened copy): a block goes back to the free blocks only
+    once its result and every view of it -- numpy or torch -- are gone; a small result never takes a huge block; beyond
+    its budget the cache forgets its oldest free blocks; a result that only a reference cycle holds comes back after a
+    collection, and a collection under the cache's lock does not deadlock.  Run twice, the second time with
+    sys.getrefcount answering 3 for everything (which marked every block free under a rule of reference counts)."""
+    import sys
+    _check_result_blocks(monkeypatch)
+    monkeypatch.setattr(sys, "getrefcount", lambda obj: 3)
+    _check_result_blocks(monkeypatch)
+
+
+def _check_result_blocks(monkeypatch):
+    import gc
+    import threading
     import torch
     from prosstt_amd import device
-    saved = list(device._result_blocks)
-    del device._result_blocks[:]
+    saved = list(device._free_blocks)
+    del device._free_blocks[:]
+
+    def free():
+        return [block.ctypes.data for block in device._free_blocks]
     try:
         a = device._result_array((300, 1000), np.int64)
         b = device._result_array((300, 1000), np.int64)
@@ -436,29 +450,54 @@ def test_pageable_result_blocks_are_recycled_only_when_nobody_holds_them():
         view = a[5:9]
         del a
         c = device._result_array((300, 1000), np.int64)
-        assert c.ctypes.data not in (pa, pb)                     # the view still holds a's block
+        assert c.ctypes.data not in (pa, pb) and free() == []   # the view still holds a's block
         pc = c.ctypes.data
         del view, c
+        assert free() == [pa, pc]
         d = device._result_array((280, 1000), np.int32)          # smaller, another type: laid over a freed block
         assert d.ctypes.data in (pa, pc) and d.dtype == np.int32 and d.shape == (280, 1000)
         pd = d.ctypes.data
         t = torch.from_numpy(d)
         del d
-        assert device._result_array((280, 1000), np.int32).ctypes.data != pd      # held through the tensor
+        x = device._result_array((280, 1000), np.int32)
+        px = x.ctypes.data
+        del x                                                    # (names, not temporaries: the block goes back now)
+        assert px != pd and pd not in free()                     # held through the tensor
         del t
-        assert device._result_array((3, 3), np.int64).ctypes.data not in (pa, pb, pc)   # far smaller: its own block
-        held = sum(x.size for x in device._result_blocks)
-        assert held >= 2 * 300 * 1000 * 8
-        old = device.RESULT_CACHE_BYTES
-        device.RESULT_CACHE_BYTES = 1000
+        assert pd in free()
+        x = device._result_array((3, 3), np.int64)
+        pe = x.ctypes.data
+        del x
+        assert pe not in (pa, pb, pc)                            # far smaller: its own block
+        assert sum(x.size for x in device._free_blocks) >= 2 * 300 * 1000 * 8 and free()[-1] == pe
+        oldest = free()[0]
+        with monkeypatch.context() as m:
+            m.setattr(device, "RESULT_CACHE_BYTES", 300 * 1000 * 8 + 1000)
+            e = device._result_array((3, 3), np.int64)           # the small block again; then over budget: the oldest goes
+            assert e.ctypes.data == pe and oldest not in free() and len(free()) == 1
+            del e
+        assert pb not in free() and np.array_equal(b, b)         # b is still the caller's: the budget never touches it
+        gc.disable()
         try:
-            device._result_array((3, 3), np.int64)
-            assert len(device._result_blocks) == 1
+            cycle = [device._result_array((300, 1000), np.int64)]
+            cycle.append(cycle)
+            pf = cycle[0].ctypes.data
+            del cycle
+            assert pf not in free()
+            collected = threading.Event()
+
+            def collect():
+                with device._result_lock:                        # (the finalizer runs inside the lock's holder)
+                    gc.collect()
+                collected.set()
+            threading.Thread(target=collect, daemon=True).start()
+            assert collected.wait(60), "a collection under the cache's lock deadlocked"
         finally:
-            device.RESULT_CACHE_BYTES = old
-        assert np.array_equal(b, b)                              # (b is still the caller's: dropping it from the cache freed nothing)
-        device._result_array((50, 50), np.int64)
+            gc.enable()
+        assert pf in free()
+        del b
+        assert pb in free()
         device.release_result_memory()
-        assert device._result_blocks == []
+        assert device._free_blocks == []
     finally:
-        device._result_blocks[:] = saved
+        device._free_blocks[:] = saved

@@ -1,6 +1,6 @@
 """
 CPU: libprosstt_amd_host.so (include/prosstt_amd_host.h) -- the int32 -> int64 widening the int64 host return runs on the
-host's threads (prosstt_amd/device.py, _to_host_widened): equal to numpy's astype for every length around the vector
+host's threads (prosstt_amd/device.py, _dense_attempt): equal to numpy's astype for every length around the vector
 width, every alignment of the destination, any thread count; NULL refused; usable from two threads at once and from a
 forked child of a process whose pool already runs.
 """

@@ -1,5 +1,5 @@
-"""End to end of the drop-in call (sample_density -> int64 / int32 ndarray) on C3 by wire format (device.WIRE) and size of the host
-library's widening pool, beside the device-widened copies, the sparse and the uint16 return.  Usage: python3 tools/e2e_threads.py"""
+"""End to end of the drop-in call (sample_density -> int64 / int32 ndarray, csr) on C3 by size of the host library's widening
+pool, beside the device-widened copies.  Usage: python3 tools/e2e_threads.py"""
 import sys
 import time
 
@@ -24,10 +24,8 @@ def call(out):
     return best
 
 
-for wire in ("u8", "u16", "i32"):
-    device.WIRE = wire
-    for threads in (8, 16, 32):
-        device.HOST_THREADS = threads
-        print("wire %s, %2d host threads: int64 %.1f ms   int32 %.1f ms   csr %.1f ms" % (wire, threads, call("numpy"), call("numpy32"), call("csr")))
+for threads in (8, 16, 32):
+    device.HOST_THREADS = threads
+    print("%2d host threads: int64 %.1f ms   int32 %.1f ms   csr %.1f ms" % (threads, call("numpy"), call("numpy32"), call("csr")))
 device.WIDEN_ON = "device"
 print("widened on the device / copied as it lies: int64 %.1f ms   int32 %.1f ms   csr %.1f ms" % (call("numpy"), call("numpy32"), call("csr")))
