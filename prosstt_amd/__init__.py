@@ -9,6 +9,11 @@ Count-matrix summaries on the device (means, variances, zeros, library sizes; no
 
     from prosstt_amd import summary
 
+Principal components of log1p(X / s) on the device (the example notebooks' route to neighbours and UMAP):
+
+    from prosstt_amd import simulation as sim, embed
+    X, pt, br, sc = sim.sample_density(t, n, alpha=a, beta=b, out="torch"); p = embed.pca(X, sc)
+
 or, for unmodified scripts that say ``from prosstt import ...``:
 
     import prosstt_amd; prosstt_amd.install_as_prosstt()

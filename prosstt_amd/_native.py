@@ -42,6 +42,11 @@ STATS_LIB_PATH = os.environ.get("PROSSTT_AMD_STATS_LIB") or os.path.join(_HERE, 
 STATS_SYMBOLS = ["prosstt_amd_stats_last_error", "prosstt_amd_stats_workspace_bytes", "prosstt_amd_stats_count_summary"]
 STATS_ACCUMULATE = 1
 
+EMBED_LIB_PATH = os.environ.get("PROSSTT_AMD_EMBED_LIB") or os.path.join(_HERE, "lib", "libprosstt_amd_embed.so")
+# every symbol include/prosstt_amd_embed.h declares
+EMBED_SYMBOLS = ["prosstt_amd_embed_last_error", "prosstt_amd_embed_workspace_bytes", "prosstt_amd_embed_gene_moments",
+                 "prosstt_amd_embed_matmul", "prosstt_amd_embed_rmatmul"]
+
 
 class NativeError(RuntimeError):
     def __init__(self, code, message):
@@ -106,6 +111,39 @@ def load_stats():
 def check_stats(code):
     if code != OK:
         raise NativeError(code, load_stats().prosstt_amd_stats_last_error().decode("utf-8", "replace"))
+
+
+_embed_lib = None
+
+
+def load_embed():
+    """libprosstt_amd_embed.so (include/prosstt_amd_embed.h: products with the log-normalised count matrix), once.
+    Raises if it has not been built."""
+    global _embed_lib
+    with _lock:
+        if _embed_lib is not None:
+            return _embed_lib
+        if not os.path.exists(EMBED_LIB_PATH):
+            raise RuntimeError("%s not found: build it with `make -C prosstt_amd/csrc/embed` (or "
+                               "`python -c 'import __graft_entry__ as g; g.build()'`). prosstt_amd has no "
+                               "CPU fallback." % EMBED_LIB_PATH)
+        import torch  # noqa: F401    (torch's HIP runtime first: see load())
+        L = ctypes.CDLL(EMBED_LIB_PATH)
+        vp, i64, u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64
+        L.prosstt_amd_embed_last_error.restype = ctypes.c_char_p
+        L.prosstt_amd_embed_workspace_bytes.argtypes = [i64, i64, i64, ctypes.POINTER(u64)]
+        L.prosstt_amd_embed_gene_moments.argtypes = [vp, vp, i64, i64, i64, vp, vp, u64, vp, vp, vp]
+        L.prosstt_amd_embed_matmul.argtypes = [vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, u64, vp]
+        L.prosstt_amd_embed_rmatmul.argtypes = [vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, u64, vp]
+        for name in EMBED_SYMBOLS[1:]:
+            getattr(L, name).restype = ctypes.c_int
+        _embed_lib = L
+        return L
+
+
+def check_embed(code):
+    if code != OK:
+        raise NativeError(code, load_embed().prosstt_amd_embed_last_error().decode("utf-8", "replace"))
 
 
 def load():
