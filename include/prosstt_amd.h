@@ -33,7 +33,7 @@ extern "C" {
 enum {
     PROSSTT_AMD_OK = 0,
     PROSSTT_AMD_EINVAL = -1,  /* bad argument */
-    PROSSTT_AMD_EDOMAIN = -2, /* a mean <= 0 or a*m+b < 1 (the reference raises ValueError there) */
+    PROSSTT_AMD_EDOMAIN = -2, /* a mean that is not positive and finite, or a*m+b < 1 (the reference raises ValueError there) */
     PROSSTT_AMD_EHIP = -3,    /* HIP runtime error */
     PROSSTT_AMD_ENOMEM = -4,
     PROSSTT_AMD_ENODEV = -5,  /* no gfx950 device visible */
@@ -112,7 +112,7 @@ int prosstt_amd_plan_order(const int32_t* row_of_cell, int64_t N, int64_t rows, 
 
 /*
  * The verdict of the PROSSTT_AMD_CHECK_DEFERRED calls since the last time, read and cleared (synchronises the stream):
- * *status = 0, PROSSTT_AMD_EDOMAIN (a mean <= 0 or alpha*m + beta < 1: where scipy's argument check behind
+ * *status = 0, PROSSTT_AMD_EDOMAIN (a mean that is not positive and finite, or alpha*m + beta < 1: where scipy's argument check behind
  * simulation.py:647-648 raises ValueError) or PROSSTT_AMD_EINVAL (a row index outside the mean tensor); the message is in
  * prosstt_amd_last_error().  Returns 0 unless the HIP runtime failed.
  */

@@ -590,3 +590,79 @@ def add_non_diff_genes(inform_expr_matrix, genes, gene_params, cell_scalings):
     out[:, :G] = inform_expr_matrix
     out[:, G:] = x.reshape((N, genes))
     return out
+
+
+# --------------------------------------------------------------------------
+# The argument check of the sampling stage, on the arrays the device is given
+# --------------------------------------------------------------------------
+
+def _device_sample_means(means_rows, row_of_cell, scaling):
+    """(N, G) binary64 mean of every sample as simulation.py:638-639 forms it, from what the device holds: the mean
+    tensor stored in binary32 (widened here), one row index and one binary64 scaling per cell."""
+    stored = np.asarray(means_rows, dtype=np.float32).astype(np.float64)
+    rows = np.asarray(row_of_cell, dtype=np.int64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return stored[rows] * np.asarray(scaling, dtype=np.float64)[:, None]
+
+
+def domain_ok(means_rows, row_of_cell, scaling, alpha, beta):
+    """(N, G) bool: the samples that pass the argument check of ``draw_counts`` (simulation.py:641-648 -- scipy's
+    ``nbinom(n=r, p=1-p).rvs()``: n > 0 and 0 < p <= 1), evaluated in binary64 through ``get_pr_umi`` exactly as
+    ``draw_counts`` does.  Means below about 1e-154 are outside what this function is for: ``m ** 2`` underflows and the
+    reference then refuses a positive mean."""
+    mu = _device_sample_means(means_rows, row_of_cell, scaling)
+    alpha = np.asarray(alpha, dtype=np.float64)
+    beta = np.asarray(beta, dtype=np.float64)
+    p, r = get_pr_umi(alpha[None, :], beta[None, :], mu)       # (elementwise: the rows are draw_counts' per-cell calls)
+    n_arg, p_arg = r, 1 - p
+    with np.errstate(invalid="ignore"):
+        return (n_arg > 0) & (p_arg > 0) & (p_arg <= 1)
+
+
+def domain_error(means_rows, row_of_cell, scaling, alpha, beta):
+    """True iff ``draw_counts`` raises "Domain error in arguments" on these inputs (no cells or no genes: never)."""
+    return not bool(np.all(domain_ok(means_rows, row_of_cell, scaling, alpha, beta)))
+
+
+def domain_ok_closed_form(means_rows, row_of_cell, scaling, alpha, beta):
+    """The same verdict per sample in the closed form the device kernels implement: a sample passes iff its mean
+    m = M*s is positive and finite and theta = alpha*m + (beta - 1) is not negative (NaN anywhere fails).  From
+    ``get_pr_umi``: s2 - m = m*theta, so n = m/theta and p = 1/(alpha*m + beta); theta = 0 gives n = inf, p = 1, which
+    scipy accepts (alpha = 0, beta = 1: all zeros)."""
+    mu = _device_sample_means(means_rows, row_of_cell, scaling)
+    alpha = np.asarray(alpha, dtype=np.float64)[None, :]
+    beta = np.asarray(beta, dtype=np.float64)[None, :]
+    with np.errstate(invalid="ignore", over="ignore"):
+        theta = alpha * mu + (beta - 1.0)
+        return (mu > 0) & (mu < np.inf) & (theta >= 0)
+
+
+def domain_rounding_band(means_rows, row_of_cell, scaling, alpha, beta, width=2.0 ** -20):
+    """(N, G) bool: the samples whose theta lies so close to zero that binary32 arithmetic may see another sign than
+    binary64: |alpha*m + beta - 1| <= width * (|alpha|*m + |beta - 1|), for positive finite m.  The device rounds alpha,
+    beta - 1, the scaling and M*s to binary32 and then forms theta with one fma: five roundings of 2^-24 each, relative
+    to |alpha|*m + |beta - 1|; the default width is 16 of those.  theta that is exactly 0 from exactly representable terms
+    (alpha = 0, beta = 1) is not in the band: every format computes 0."""
+    mu = _device_sample_means(means_rows, row_of_cell, scaling)
+    alpha = np.asarray(alpha, dtype=np.float64)[None, :]
+    beta = np.asarray(beta, dtype=np.float64)[None, :]
+    with np.errstate(invalid="ignore", over="ignore"):
+        theta = alpha * mu + (beta - 1.0)
+        size = np.abs(alpha) * mu + np.abs(beta - 1.0)
+        band = (mu > 0) & (mu < np.inf) & (np.abs(theta) <= width * size)
+    return band & ~((alpha == 0) & (beta == 1))
+
+
+def domain_cancellation_band(means_rows, row_of_cell, scaling, alpha, beta, width=2.0 ** -50):
+    """(N, G) bool: the samples on which the REFERENCE's own arithmetic cannot be trusted with the sign of theta.
+    ``get_pr_umi`` forms s2 = alpha*m^2 + beta*m (rounded, about 2^-53 relative to |alpha|*m^2 + |beta|*m) and then
+    s2 - m = m*theta: where |theta| <= width * (|alpha|*m + |beta|) the difference is rounding noise (alpha = -0.1,
+    beta = 1, m = 1e-38: s2 rounds to m, the reference sees theta = 0 and accepts a sample whose theta is negative).
+    The default width is 8 roundings.  alpha = 0, beta = 1 is exact (s2 = m) and not in the band."""
+    mu = _device_sample_means(means_rows, row_of_cell, scaling)
+    alpha = np.asarray(alpha, dtype=np.float64)[None, :]
+    beta = np.asarray(beta, dtype=np.float64)[None, :]
+    with np.errstate(invalid="ignore", over="ignore"):
+        theta = alpha * mu + (beta - 1.0)
+        band = (mu > 0) & (mu < np.inf) & (np.abs(theta) <= width * (np.abs(alpha) * mu + np.abs(beta)))
+    return band & ~((alpha == 0) & (beta == 1))

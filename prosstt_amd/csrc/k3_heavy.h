@@ -546,17 +546,21 @@ __global__ __launch_bounds__(kHeavyBlock) void sample_counts_heavy_kernel(
     // (check_words: the ctx's flag words; NULL: an unchecked call, or the caller has verified alpha >= 0 and beta >= 1).
     // The preparation kernel has done the per-cell and per-gene parts and raised check_words[check_request] iff some gene
     // has alpha < 0 or beta < 1: only then can alpha*m + beta < 1 happen with every mean positive, and only then is the
-    // whole matrix looked at here -- m = M*s <= 0 (or NaN) or alpha*m + beta - 1 < 0 anywhere sets the verdict word.  It
-    // rides in this kernel so that a checked call launches nothing more than an unchecked one.  (A block takes whole
-    // cells and walks their genes: no division per sample.)
+    // whole matrix looked at here -- a stored mean M that is not a positive finite number, or alpha*m + beta - 1 < 0 with
+    // m = M*s, anywhere sets the verdict word.  The scaling s was judged in binary64 by the preparation kernel and the
+    // product M*s is NOT tested against 0 here: a product that underflows binary32 (1e-30 * 1e-10) is a positive mean in
+    // the reference, and the per-row / per-cell tests of a call without such a gene accept it too -- theta alone is
+    // formed from it (then beta - 1, whose sign is theta's).  It rides in this kernel so that a checked call launches
+    // nothing more than an unchecked one.  (A block takes whole cells and walks their genes: no division per sample.)
     if (check_words && check_words[check_request] != 0 && check_words[check_bad_row] == 0) {
         bool bad = false;
         for (int64_t n = blockIdx.x; n < N; n += gridDim.x) {
             const float s = scal[n];
             const float* mrow = means + (int64_t)row_of_cell[n] * G;
             for (int32_t g = tid; g < G; g += kHeavyBlock) {
-                const float m = mrow[g] * s;
-                bad = bad || !(m > 0.0f) || (PRNB_FMA(ga[g], m, gbm1[g]) < 0.0f);
+                const float M = mrow[g];
+                const float m = M * s;
+                bad = bad || !(M > 0.0f && M < __builtin_inff()) || (PRNB_FMA(ga[g], m, gbm1[g]) < 0.0f);
             }
         }
         if (bad) check_words[check_verdict] = 1;

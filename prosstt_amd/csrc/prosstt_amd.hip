@@ -77,7 +77,7 @@ struct prosstt_amd_ctx {
     uint64_t list_regions = 0;
     int64_t list_groups = 0, list_strip_cells = 0;
     int heavy_grid = 1280;       // blocks of K3h that are resident at once on this device (5 per CU: its 30 496 B of LDS)
-    // domain check: one byte per row of the mean tensor last scanned ("has an entry that is not > 0"), and which tensor that was
+    // domain check: one byte per row of the mean tensor last scanned ("has an entry that is not in (0, inf)"), and which tensor that was
     uint8_t* row_bad = nullptr;
     size_t row_bad_cap = 0;
     const float* row_bad_means = nullptr;
@@ -151,10 +151,13 @@ struct Staging {
 // parameters (and the zero-test factor), the per-cell records of the streaming kernel (k3::CellInfo;
 // N + 4 entries, the last cell repeated; skipped when `info` is NULL), and the call's flag words.
 // With `row_bad` (a checked call) it is also the per-cell and per-gene part of the domain check: scipy's argument
-// check in the reference fails iff some mean m = M*s is <= 0 (or NaN) or some theta = a*m + b - 1 is < 0.  With every
-// scaling > 0 the first holds iff a USED row of the mean tensor has an entry that is not > 0 (row_bad, from
-// row_flags_kernel); with every a >= 0 and b >= 1 the second cannot happen -- only when a gene has a < 0 or b < 1
-// is the full N x G test needed (flags[kFullReq + parity], read at the end of K3h).
+// check in the reference fails iff some mean m = M*s is not a positive finite number (zero, negative, infinite, NaN) or
+// some theta = a*m + b - 1 is < 0.  The first is decided factor by factor, so that no product can hide it: a scaling
+// that is not in (0, inf) -- tested in binary64, as given: 1e-50 is positive though it is 0 in binary32 -- or a USED row of
+// the mean tensor with an entry that is not in (0, inf) (row_bad, from row_flags_kernel).  With every a >= 0 and b >= 1
+// the second cannot happen -- only when a gene has a < 0 or b < 1 is the full N x G test needed (flags[kFullReq + parity],
+// read at the end of K3h), and that pass looks at theta only: the same sample gets the same verdict whatever the other
+// genes are.
 __global__ void prep_kernel(const double* __restrict__ scaling, int64_t N,
                             const double* __restrict__ alpha, const double* __restrict__ beta, int32_t G,
                             float* __restrict__ scal_f, float* __restrict__ a_f,
@@ -173,12 +176,12 @@ __global__ void prep_kernel(const double* __restrict__ scaling, int64_t N,
         flags[kFullReq + (parity ^ 1u)] = 0;  // the NEXT call's full-test request (this call's was cleared by the previous one)
     }
     if (i < N) {
-        const float s = (float)scaling[i];
-        scal_f[i] = s;
+        const double sd = scaling[i];
+        scal_f[i] = (float)sd;
         if (row_bad) {
             const int64_t r = row_of_cell[i];
             if (r < 0 || r >= rows) flags[kStickyRow] = 1;     // reported as EINVAL, never read through
-            else if (row_bad[r] || !(s > 0.0f)) flags[kStickyDomain] = 1;
+            else if (row_bad[r] || !(sd > 0.0 && sd < __builtin_inf())) flags[kStickyDomain] = 1;
         }
     }
     if (i < G) {
@@ -552,7 +555,8 @@ __global__ __launch_bounds__(256) void means_from_rel_kernel(const double* __res
 }
 
 // ---- domain check of the streaming path (PROSSTT_AMD_CHECK_DOMAIN / _CHECK_DEFERRED; see prep_kernel) ----------
-// row_bad[r] = 1 iff row r of the mean tensor has an entry that is not > 0 (zero, negative, NaN): one block per row.
+// row_bad[r] = 1 iff row r of the mean tensor has an entry that is not a positive finite number (zero, negative, NaN,
+// infinite -- the reference's p is NaN for an infinite mean, whatever alpha and beta are): one block per row.
 // Scanned once per mean tensor (the ctx remembers which tensor its flags belong to).
 __global__ __launch_bounds__(256) void row_flags_kernel(const float* __restrict__ means, int64_t rows, int64_t G,
                                                         uint8_t* __restrict__ row_bad)
@@ -560,7 +564,10 @@ __global__ __launch_bounds__(256) void row_flags_kernel(const float* __restrict_
     for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
         const float* row = means + r * G;
         int bad = 0;
-        for (int64_t g = threadIdx.x; g < G; g += blockDim.x) bad |= !(row[g] > 0.0f);
+        for (int64_t g = threadIdx.x; g < G; g += blockDim.x) {
+            const float v = row[g];
+            bad |= !(v > 0.0f && v < __builtin_inff());
+        }
         bad = __syncthreads_or(bad);
         if (threadIdx.x == 0) row_bad[r] = (uint8_t)(bad != 0);
     }
@@ -835,7 +842,7 @@ static int domain_verdict(prosstt_amd_ctx* c, int64_t rows, int* verdict)
     }
     if (c->h_scratch[kStickyDomain]) {
         *verdict = PROSSTT_AMD_EDOMAIN;
-        return fail(PROSSTT_AMD_EDOMAIN, "Domain error in arguments: a mean <= 0 or alpha*m + beta < 1");
+        return fail(PROSSTT_AMD_EDOMAIN, "Domain error in arguments: a mean that is not positive and finite, or alpha*m + beta < 1");
     }
     return 0;
 }

@@ -581,10 +581,13 @@ def draw_counts(tree, pseudotime, branches, scalings, alpha, beta, *, seed=None,
               row i belongs to cell ``cell_of_row[i]``; ``result.in_plan_order()`` gathers.  "plan": a plain device
               tensor whose row n is cell n; the cells are then presented as planned (2 to 5 % slower, and on a
               32-branch tree 1.75 x the HBM traffic: the mean tensor's rows are fetched once per cell).
-      strict  raise ``ValueError`` where scipy's argument check would (an exact-zero
-              mean, or alpha*m + beta < 1); the test rides in the call's own kernels (the per-row flags of
+      strict  raise ``ValueError`` where scipy's argument check would: a mean m = M*s that is not a positive
+              finite number (a zero, negative, NaN or infinite entry of ``tree.means`` or scaling; the scaling
+              is judged as the binary64 number given, so 1e-50 is valid), or alpha*m + beta < 1 (formed in
+              binary32: within a relative 2^-20 of equality the verdict may differ from binary64's; alpha = 0,
+              beta = 1 is exact and valid).  The test rides in the call's own kernels (the per-row flags of
               the mean tensor are kept until the tensor changes) and costs no launch and no extra
-              synchronisation.  False skips it.
+              synchronisation.  False skips it: the offending samples are 0.
     """
     no_cells = len(branches)
     if len(pseudotime) != no_cells or len(scalings) != no_cells:
@@ -641,9 +644,9 @@ def _discard_verdict(ctx):
         pass
 
 
-def add_non_diff_genes(inform_expr_matrix, genes, gene_params, cell_scalings, *, seed=None):
+def add_non_diff_genes(inform_expr_matrix, genes, gene_params, cell_scalings, *, seed=None, strict=True):
     """Append ``genes`` non-differential genes (simulation.py:654-675): the same sampler
-    with one constant mean row; returns float64 like the reference."""
+    with one constant mean row; returns float64 like the reference.  ``strict``: as in ``draw_counts``."""
     N, G = inform_expr_matrix.shape
     if seed is None:
         lo, hi = random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
@@ -654,7 +657,7 @@ def add_non_diff_genes(inform_expr_matrix, genes, gene_params, cell_scalings, *,
                               np.asarray(cell_scalings, dtype=np.float64),
                               np.broadcast_to(np.asarray(gene_params["alpha"], dtype=np.float64), (genes,)),
                               np.broadcast_to(np.asarray(gene_params["beta"], dtype=np.float64), (genes,)),
-                              seed=seed)
+                              seed=seed, check_domain=bool(strict))
     fusion = np.zeros((N, G + genes))
     fusion[:, 0:G] = inform_expr_matrix
     fusion[:, G:] = extra.cpu().numpy()
