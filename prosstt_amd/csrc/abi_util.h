@@ -1,0 +1,93 @@
+// What a library that reads the int32 count matrix where it lies needs besides its kernels: the C ABI's error plumbing,
+// the refusals of a matrix argument, and the launch geometry of a "strip of genes over a range of rows" kernel.
+// Internal: included by stats/count_summary.hip and embed/embed.hip, each a single translation unit, and not installed
+// under include/.  The including file defines ABI_EINVAL and ABI_EHIP (its header's error codes) first.
+// (prosstt_amd.hip keeps macros of its own: its ABI has an ENOMEM code and reports e.what().)
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <new>
+
+#if !defined(ABI_EINVAL) || !defined(ABI_EHIP)
+#error "define ABI_EINVAL and ABI_EHIP before including abi_util.h"
+#endif
+
+#define ABI_EXPORT extern "C" __attribute__((visibility("default")))
+// the tail of an entry point's function-try-block: no exception crosses the C ABI
+#define ABI_CATCH                                                                                  \
+    catch (const std::bad_alloc&) { return fail(ABI_EINVAL, "out of host memory"); }               \
+    catch (...) { return fail(ABI_EINVAL, "unexpected exception"); }
+
+static thread_local char g_err[512] = "";      // what the library's *_last_error returns
+
+static int fail(int code, const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                                     \
+    do {                                                                                                  \
+        hipError_t e_ = (expr);                                                                           \
+        if (e_ != hipSuccess)                                                                             \
+            return fail(ABI_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);    \
+    } while (0)
+
+namespace {
+
+constexpr int kThreads = 256;               // 4 waves
+constexpr int kStrip = 4 * kThreads;        // genes per block of a strip kernel: one 16-byte load per lane and row
+constexpr int kStripMinRows = 64;           // a strip kernel's block takes at least this many rows (count_summary's batch)
+constexpr int64_t kTargetBlocks = 1024;     // one round of blocks: about four per CU on 256 CUs
+
+inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+inline size_t pad(size_t b) { return (b + 255) & ~size_t(255); }
+
+// May every row be read with loads of `elems` counts (16 bytes: 4, 8 bytes: 2)?
+inline bool aligned(const void* p, int64_t ld, int elems)
+{
+    return ((uintptr_t)p % (4 * elems) == 0) && (ld % elems == 0);
+}
+
+// The refusals of a matrix argument.  The bounds on G and their messages differ between the libraries and stay there.
+inline bool cells_out_of_range(int64_t N) { return N < 1 || N >= (int64_t(1) << 31); }
+
+inline int stride_below_row(int64_t ld, int64_t G)
+{
+    return fail(ABI_EINVAL, "row stride %lld is below the row length %lld", (long long)ld, (long long)G);
+}
+
+inline int workspace_too_small(uint64_t have, size_t need)
+{
+    return fail(ABI_EINVAL, "workspace of %llu bytes, %llu needed", (unsigned long long)have, (unsigned long long)need);
+}
+
+// The grid of a strip kernel: blockIdx.x owns the genes [kStrip x, kStrip (x + 1)), blockIdx.y the rows
+// [rows_per_block y, rows_per_block (y + 1)).  All zeros when G == 0.  (The kernels' mapping of a lane to its four genes
+// stays written out in each: as a shared __device__ helper it changed count_summary_kernel's register allocation.)
+struct StripGeometry {
+    int64_t strips = 0, row_blocks = 0, rows_per_block = 0;
+};
+
+inline StripGeometry strip_geometry(int64_t N, int64_t G)
+{
+    StripGeometry g;
+    g.strips = cdiv(G, kStrip);
+    if (g.strips > 0) {
+        // (rounded down: a second round of a few blocks would cost as much as the first)
+        const int64_t rb = clamp64(kTargetBlocks / g.strips, 1, cdiv(N, kStripMinRows));
+        g.rows_per_block = cdiv(N, rb);
+        g.row_blocks = cdiv(N, g.rows_per_block);
+    }
+    return g;
+}
+
+}  // namespace

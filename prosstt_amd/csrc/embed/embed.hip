@@ -17,57 +17,24 @@
 // (lane >> 5) supplies index 16h + s of the step, for A and for the panel alike.  C/D map of a 32x32 tile: column
 // lane & 31, row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  lp = l rounded up to 32: the panel's extra columns and the
 // masked rows and genes of a step are zeros, so every l in 1..128 runs the same code.
-#include <hip/hip_runtime.h>
-
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
-#include <new>
-
 #include "../../../include/prosstt_amd_embed.h"
 
-#define PE_EXPORT extern "C" __attribute__((visibility("default")))
-#define PE_CATCH                                                                                                  \
-    catch (const std::bad_alloc&) { return fail(PROSSTT_AMD_EMBED_EINVAL, "out of host memory"); }               \
-    catch (...) { return fail(PROSSTT_AMD_EMBED_EINVAL, "unexpected exception"); }
-
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess)                                                                             \
-            return fail(PROSSTT_AMD_EMBED_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#define ABI_EINVAL PROSSTT_AMD_EMBED_EINVAL
+#define ABI_EHIP PROSSTT_AMD_EMBED_EHIP
+#include "../abi_util.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kThreads = 256;               // 4 waves
 constexpr int kStep = 32;                   // genes (matmul) or rows (rmatmul) per step of the k loop
 constexpr int kRowsMM = 128;                // matmul: rows per block, 32 per wave
 constexpr int kGenesRM = 256;               // rmatmul: genes per block, 64 per wave
-constexpr int kStripM = 4 * kThreads;       // moments: genes per block
-constexpr int64_t kTargetBlocks = 1024;     // about four blocks per CU on 256 CUs
 constexpr float kLn2 = 0.693147180559945309f;
-
-int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-size_t pad(size_t b) { return (b + 255) & ~size_t(255); }
 
 struct Geometry {
     int64_t lp = 0;                                   // panel width rounded up to 32
-    int64_t m_row_blocks = 0, m_rows_per_block = 0;   // moments
+    StripGeometry m;                                  // moments
     int64_t mm_parts = 0, mm_genes_per_part = 0;      // matmul (blocks: ceil(N / 128) x parts)
     int64_t rm_row_blocks = 0, rm_rows_per_block = 0; // rmatmul (blocks: ceil(G / 256) x row_blocks)
     size_t m_bytes = 0, mm_bytes = 0, rm_bytes = 0, bytes = 0;
@@ -77,11 +44,8 @@ Geometry geometry(int64_t N, int64_t G, int64_t l)
 {
     Geometry g;
     g.lp = cdiv(l, 32) * 32;
-    const int64_t strips = cdiv(G, kStripM);
-    int64_t rb = clamp64(kTargetBlocks / strips, 1, cdiv(N, 64));
-    g.m_rows_per_block = cdiv(N, rb);
-    g.m_row_blocks = cdiv(N, g.m_rows_per_block);
-    g.m_bytes = 2 * pad((size_t)g.m_row_blocks * (size_t)G * 8);
+    g.m = strip_geometry(N, G);
+    g.m_bytes = 2 * pad((size_t)g.m.row_blocks * (size_t)G * 8);
 
     const int64_t chunks = cdiv(G, kStep);
     const int64_t parts = clamp64(kTargetBlocks / cdiv(N, kRowsMM), 1, chunks);
@@ -90,7 +54,7 @@ Geometry geometry(int64_t N, int64_t G, int64_t l)
     g.mm_bytes = pad((size_t)g.mm_parts * (size_t)N * (size_t)g.lp * 4);
 
     const int64_t row_steps = cdiv(N, kStep);
-    rb = clamp64(kTargetBlocks / cdiv(G, kGenesRM), 1, row_steps);
+    const int64_t rb = clamp64(kTargetBlocks / cdiv(G, kGenesRM), 1, row_steps);
     g.rm_rows_per_block = cdiv(row_steps, rb) * kStep;
     g.rm_row_blocks = cdiv(N, g.rm_rows_per_block);
     g.rm_bytes = pad((size_t)g.rm_row_blocks * (size_t)G * (size_t)g.lp * 4);
@@ -126,11 +90,11 @@ __global__ __launch_bounds__(kThreads) void embed_moments_kernel(const int32_t* 
                                                                  double* __restrict__ s2slab, uint32_t* __restrict__ status)
 {
     const int tid = threadIdx.x;
-    const int64_t gbase = (int64_t)blockIdx.x * kStripM;
+    const int64_t gbase = (int64_t)blockIdx.x * kStrip;
     const int64_t g0 = VEC ? gbase + 4 * tid : gbase + tid;
     const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
     const int64_t r1 = (r0 + rows_per_block < N) ? r0 + rows_per_block : N;
-    const bool full = gbase + kStripM <= G;
+    const bool full = gbase + kStrip <= G;
     double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
     int32_t neg = 0;
 #pragma unroll 2
@@ -410,10 +374,10 @@ int sum_panels(hipStream_t st, const float* slab, int64_t parts, int64_t rows, i
 
 int check_common(const int32_t* X, int64_t N, int64_t G, int64_t ld, const float* inv_size, void* ws, uint32_t* status)
 {
-    if (N < 1 || N >= (int64_t(1) << 31) || G < 1)
+    if (cells_out_of_range(N) || G < 1)
         return fail(PROSSTT_AMD_EMBED_EINVAL, "need 1 <= N < 2^31 and G >= 1 (got N = %lld, G = %lld)", (long long)N,
                     (long long)G);
-    if (ld < G) return fail(PROSSTT_AMD_EMBED_EINVAL, "row stride %lld is below the row length %lld", (long long)ld, (long long)G);
+    if (ld < G) return stride_below_row(ld, G);
     if (!X || !inv_size || !ws || !status) return fail(PROSSTT_AMD_EMBED_EINVAL, "NULL argument");
     return 0;
 }
@@ -424,65 +388,52 @@ int check_l(int64_t l)
     return 0;
 }
 
-int check_ws(size_t need, uint64_t have)
-{
-    if (have < need)
-        return fail(PROSSTT_AMD_EMBED_EINVAL, "workspace of %llu bytes, %llu needed", (unsigned long long)have,
-                    (unsigned long long)need);
-    return 0;
-}
-
-bool aligned(const void* p, int64_t ld, int elems)
-{
-    return ((uintptr_t)p % (4 * elems) == 0) && (ld % elems == 0);
-}
-
 }  // namespace
 
-PE_EXPORT const char* prosstt_amd_embed_last_error(void) { return g_err; }
+ABI_EXPORT const char* prosstt_amd_embed_last_error(void) { return g_err; }
 
-PE_EXPORT int prosstt_amd_embed_workspace_bytes(int64_t N, int64_t G, int64_t l, uint64_t* bytes) try
+ABI_EXPORT int prosstt_amd_embed_workspace_bytes(int64_t N, int64_t G, int64_t l, uint64_t* bytes) try
 {
     if (!bytes) return fail(PROSSTT_AMD_EMBED_EINVAL, "NULL argument");
-    if (N < 1 || N >= (int64_t(1) << 31) || G < 1) return fail(PROSSTT_AMD_EMBED_EINVAL, "need 1 <= N < 2^31 and G >= 1");
+    if (cells_out_of_range(N) || G < 1) return fail(PROSSTT_AMD_EMBED_EINVAL, "need 1 <= N < 2^31 and G >= 1");
     if (int rc = check_l(l)) return rc;
     *bytes = geometry(N, G, l).bytes;
     return 0;
 }
-PE_CATCH
+ABI_CATCH
 
-PE_EXPORT int prosstt_amd_embed_gene_moments(void* stream, const int32_t* X, int64_t N, int64_t G, int64_t ld,
-                                             const float* inv_size, void* ws, uint64_t ws_bytes, double* S1, double* S2,
-                                             uint32_t* status) try
+ABI_EXPORT int prosstt_amd_embed_gene_moments(void* stream, const int32_t* X, int64_t N, int64_t G, int64_t ld,
+                                              const float* inv_size, void* ws, uint64_t ws_bytes, double* S1, double* S2,
+                                              uint32_t* status) try
 {
     if (int rc = check_common(X, N, G, ld, inv_size, ws, status)) return rc;
     if (!S1 || !S2) return fail(PROSSTT_AMD_EMBED_EINVAL, "NULL argument");
     const Geometry geo = geometry(N, G, 1);
-    if (int rc = check_ws(geo.m_bytes, ws_bytes)) return rc;
+    if (ws_bytes < geo.m_bytes) return workspace_too_small(ws_bytes, geo.m_bytes);
     hipStream_t st = (hipStream_t)stream;
     double* s1 = (double*)ws;
     double* s2 = (double*)((char*)ws + geo.m_bytes / 2);
-    const dim3 grid((unsigned)cdiv(G, kStripM), (unsigned)geo.m_row_blocks);
+    const dim3 grid((unsigned)geo.m.strips, (unsigned)geo.m.row_blocks);
     if (aligned(X, ld, 4))
-        embed_moments_kernel<true><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, inv_size, geo.m_rows_per_block, s1, s2, status);
+        embed_moments_kernel<true><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, inv_size, geo.m.rows_per_block, s1, s2, status);
     else
-        embed_moments_kernel<false><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, inv_size, geo.m_rows_per_block, s1, s2, status);
+        embed_moments_kernel<false><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, inv_size, geo.m.rows_per_block, s1, s2, status);
     HIP_TRY(hipGetLastError());
-    embed_sum_moments_kernel<<<dim3((unsigned)cdiv(G, kThreads)), dim3(kThreads), 0, st>>>(s1, s2, G, geo.m_row_blocks, S1, S2);
+    embed_sum_moments_kernel<<<dim3((unsigned)cdiv(G, kThreads)), dim3(kThreads), 0, st>>>(s1, s2, G, geo.m.row_blocks, S1, S2);
     HIP_TRY(hipGetLastError());
     return 0;
 }
-PE_CATCH
+ABI_CATCH
 
-PE_EXPORT int prosstt_amd_embed_matmul(void* stream, const int32_t* X, int64_t N, int64_t G, int64_t ld,
-                                       const float* inv_size, const float* W, int64_t l, float* Y, void* ws,
-                                       uint64_t ws_bytes, uint32_t* status) try
+ABI_EXPORT int prosstt_amd_embed_matmul(void* stream, const int32_t* X, int64_t N, int64_t G, int64_t ld,
+                                        const float* inv_size, const float* W, int64_t l, float* Y, void* ws,
+                                        uint64_t ws_bytes, uint32_t* status) try
 {
     if (int rc = check_common(X, N, G, ld, inv_size, ws, status)) return rc;
     if (int rc = check_l(l)) return rc;
     if (!W || !Y) return fail(PROSSTT_AMD_EMBED_EINVAL, "NULL argument");
     const Geometry geo = geometry(N, G, l);
-    if (int rc = check_ws(geo.mm_bytes, ws_bytes)) return rc;
+    if (ws_bytes < geo.mm_bytes) return workspace_too_small(ws_bytes, geo.mm_bytes);
     hipStream_t st = (hipStream_t)stream;
     float* slab = (float*)ws;
     const dim3 grid((unsigned)cdiv(N, kRowsMM), (unsigned)geo.mm_parts);
@@ -502,17 +453,17 @@ PE_EXPORT int prosstt_amd_embed_matmul(void* stream, const int32_t* X, int64_t N
     HIP_TRY(hipGetLastError());
     return sum_panels(st, slab, geo.mm_parts, N, geo.lp, l, Y);
 }
-PE_CATCH
+ABI_CATCH
 
-PE_EXPORT int prosstt_amd_embed_rmatmul(void* stream, const int32_t* X, int64_t N, int64_t G, int64_t ld,
-                                        const float* inv_size, const float* Q, int64_t l, float* Z, void* ws,
-                                        uint64_t ws_bytes, uint32_t* status) try
+ABI_EXPORT int prosstt_amd_embed_rmatmul(void* stream, const int32_t* X, int64_t N, int64_t G, int64_t ld,
+                                         const float* inv_size, const float* Q, int64_t l, float* Z, void* ws,
+                                         uint64_t ws_bytes, uint32_t* status) try
 {
     if (int rc = check_common(X, N, G, ld, inv_size, ws, status)) return rc;
     if (int rc = check_l(l)) return rc;
     if (!Q || !Z) return fail(PROSSTT_AMD_EMBED_EINVAL, "NULL argument");
     const Geometry geo = geometry(N, G, l);
-    if (int rc = check_ws(geo.rm_bytes, ws_bytes)) return rc;
+    if (ws_bytes < geo.rm_bytes) return workspace_too_small(ws_bytes, geo.rm_bytes);
     hipStream_t st = (hipStream_t)stream;
     float* slab = (float*)ws;
     const dim3 grid((unsigned)cdiv(G, kGenesRM), (unsigned)geo.rm_row_blocks);
@@ -532,4 +483,4 @@ PE_EXPORT int prosstt_amd_embed_rmatmul(void* stream, const int32_t* X, int64_t 
     HIP_TRY(hipGetLastError());
     return sum_panels(st, slab, geo.rm_row_blocks, G, geo.lp, l, Z);
 }
-PE_CATCH
+ABI_CATCH

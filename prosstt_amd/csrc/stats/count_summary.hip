@@ -15,73 +15,33 @@
 //   per gene over the row blocks: S1 < 2^62, S2 in 128 bits (low word, high word with carry), zeros in u64
 //   per row in one strip (1024 genes): sum < 2^41 and zeros <= 1024, packed as sum | zeros << 48 -- the packed words of
 //     the lanes, waves and the four waves of a block add without one field reaching the other
-#include <hip/hip_runtime.h>
-
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
-#include <new>
-
 #include "../../../include/prosstt_amd_stats.h"
 
-#define PS_EXPORT extern "C" __attribute__((visibility("default")))
-#define PS_CATCH                                                                                                  \
-    catch (const std::bad_alloc&) { return fail(PROSSTT_AMD_STATS_EINVAL, "out of host memory"); }               \
-    catch (...) { return fail(PROSSTT_AMD_STATS_EINVAL, "unexpected exception"); }
-
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess)                                                                             \
-            return fail(PROSSTT_AMD_STATS_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#define ABI_EINVAL PROSSTT_AMD_STATS_EINVAL
+#define ABI_EHIP PROSSTT_AMD_STATS_EHIP
+#include "../abi_util.h"
 
 namespace {
 
-constexpr int kThreads = 256;               // 4 waves
-constexpr int kStrip = 4 * kThreads;        // genes per block: one 16-byte load per lane and row
 constexpr int kBatch = 64;                  // rows whose per-row partials wait in LDS between two block barriers
-constexpr int64_t kTargetBlocks = 1024;     // one round of blocks: 4 per CU (16 waves, 124 VGPRs each) on 256 CUs
 constexpr uint64_t kSumMask = (uint64_t(1) << 48) - 1;
 
 struct Geometry {
-    int64_t strips = 0, row_blocks = 0, rows_per_block = 0;
+    StripGeometry grid;
     size_t s1 = 0, s2lo = 0, s2hi = 0, z = 0, rows = 0, bytes = 0;   // offsets of the slabs in the workspace
 };
-
-size_t pad(size_t b) { return (b + 255) & ~size_t(255); }
 
 Geometry geometry(int64_t N, int64_t G)
 {
     Geometry g;
-    g.strips = (G + kStrip - 1) / kStrip;
-    if (g.strips > 0) {
-        int64_t rb = kTargetBlocks / g.strips;                   // (rounded down: a second round of a few blocks would
-                                                                  //  cost as much as the first)
-        const int64_t most = (N + kBatch - 1) / kBatch;          // at least one batch of rows per block
-        if (rb > most) rb = most;
-        if (rb < 1) rb = 1;
-        g.rows_per_block = (N + rb - 1) / rb;
-        g.row_blocks = (N + g.rows_per_block - 1) / g.rows_per_block;
-    }
-    const size_t cells = (size_t)g.row_blocks * (size_t)G;
+    g.grid = strip_geometry(N, G);
+    const size_t cells = (size_t)g.grid.row_blocks * (size_t)G;
     g.s1 = 0;
     g.s2lo = g.s1 + pad(cells * 8);
     g.s2hi = g.s2lo + pad(cells * 8);
     g.z = g.s2hi + pad(cells * 4);
     g.rows = g.z + pad(cells * 4);
-    g.bytes = g.rows + pad((size_t)g.strips * (size_t)N * 8);
+    g.bytes = g.rows + pad((size_t)g.grid.strips * (size_t)N * 8);
     return g;
 }
 
@@ -284,49 +244,47 @@ __global__ __launch_bounds__(64) void count_summary_rows_kernel(const uint64_t* 
 
 }  // namespace
 
-PS_EXPORT const char* prosstt_amd_stats_last_error(void) { return g_err; }
+ABI_EXPORT const char* prosstt_amd_stats_last_error(void) { return g_err; }
 
-PS_EXPORT int prosstt_amd_stats_workspace_bytes(int64_t N, int64_t G, uint64_t* bytes) try
+ABI_EXPORT int prosstt_amd_stats_workspace_bytes(int64_t N, int64_t G, uint64_t* bytes) try
 {
     if (!bytes) return fail(PROSSTT_AMD_STATS_EINVAL, "NULL argument");
-    if (N < 1 || N >= (int64_t(1) << 31) || G < 0) return fail(PROSSTT_AMD_STATS_EINVAL, "need 1 <= N < 2^31 and G >= 0");
+    if (cells_out_of_range(N) || G < 0) return fail(PROSSTT_AMD_STATS_EINVAL, "need 1 <= N < 2^31 and G >= 0");
     *bytes = geometry(N, G).bytes;
     return 0;
 }
-PS_CATCH
+ABI_CATCH
 
-PS_EXPORT int prosstt_amd_stats_count_summary(void* stream, const int32_t* X, int64_t N, int64_t G, int64_t ld,
-                                              void* workspace, uint64_t workspace_bytes,
-                                              uint64_t* gene_sum, uint64_t* gene_sumsq, uint64_t* gene_zeros,
-                                              uint64_t* cell_total, uint64_t* cell_zeros, uint32_t* status,
-                                              uint32_t flags) try
+ABI_EXPORT int prosstt_amd_stats_count_summary(void* stream, const int32_t* X, int64_t N, int64_t G, int64_t ld,
+                                               void* workspace, uint64_t workspace_bytes,
+                                               uint64_t* gene_sum, uint64_t* gene_sumsq, uint64_t* gene_zeros,
+                                               uint64_t* cell_total, uint64_t* cell_zeros, uint32_t* status,
+                                               uint32_t flags) try
 {
-    if (N < 1 || N >= (int64_t(1) << 31) || G < 0) return fail(PROSSTT_AMD_STATS_EINVAL, "need 1 <= N < 2^31 and G >= 0");
-    if (ld < G) return fail(PROSSTT_AMD_STATS_EINVAL, "row stride %lld is below the row length %lld", (long long)ld, (long long)G);
+    if (cells_out_of_range(N) || G < 0) return fail(PROSSTT_AMD_STATS_EINVAL, "need 1 <= N < 2^31 and G >= 0");
+    if (ld < G) return stride_below_row(ld, G);
     if (!cell_total || !cell_zeros || !status || (G > 0 && (!X || !gene_sum || !gene_sumsq || !gene_zeros)))
         return fail(PROSSTT_AMD_STATS_EINVAL, "NULL argument");
     if (flags & ~PROSSTT_AMD_STATS_ACCUMULATE) return fail(PROSSTT_AMD_STATS_EINVAL, "unknown flag bits 0x%x", flags);
     const Geometry geo = geometry(N, G);
-    if (!workspace || workspace_bytes < geo.bytes)
-        return fail(PROSSTT_AMD_STATS_EINVAL, "workspace of %llu bytes, %llu needed", (unsigned long long)workspace_bytes,
-                    (unsigned long long)geo.bytes);
+    if (!workspace || workspace_bytes < geo.bytes) return workspace_too_small(workspace_bytes, geo.bytes);
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)workspace;
     const Slabs s{(uint64_t*)(w + geo.s1), (uint64_t*)(w + geo.s2lo), (uint32_t*)(w + geo.s2hi), (uint32_t*)(w + geo.z),
                   (uint64_t*)(w + geo.rows)};
     if (G > 0) {
-        const dim3 grid((unsigned)geo.strips, (unsigned)geo.row_blocks);
-        const bool vec = ((uintptr_t)X % 16 == 0) && (ld % 4 == 0);
-        if (vec) count_summary_kernel<true><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, geo.rows_per_block, s, status);
-        else count_summary_kernel<false><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, geo.rows_per_block, s, status);
+        const dim3 grid((unsigned)geo.grid.strips, (unsigned)geo.grid.row_blocks);
+        const int64_t rows = geo.grid.rows_per_block;
+        if (aligned(X, ld, 4)) count_summary_kernel<true><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, rows, s, status);
+        else count_summary_kernel<false><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, rows, s, status);
         HIP_TRY(hipGetLastError());
         count_summary_genes_kernel<<<dim3((unsigned)((G + 63) / 64)), dim3(256), 0, st>>>(
-            s, G, geo.row_blocks, gene_sum, gene_sumsq, gene_zeros, (flags & PROSSTT_AMD_STATS_ACCUMULATE) ? 1 : 0);
+            s, G, geo.grid.row_blocks, gene_sum, gene_sumsq, gene_zeros, (flags & PROSSTT_AMD_STATS_ACCUMULATE) ? 1 : 0);
         HIP_TRY(hipGetLastError());
     }
-    count_summary_rows_kernel<<<dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st>>>(s.rows, N, geo.strips, cell_total,
+    count_summary_rows_kernel<<<dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st>>>(s.rows, N, geo.grid.strips, cell_total,
                                                                                    cell_zeros);
     HIP_TRY(hipGetLastError());
     return 0;
 }
-PS_CATCH
+ABI_CATCH

@@ -860,6 +860,68 @@ class PresentedCounts:
         return host_return(self.counts, out, row_order=self.cell_of_row)
 
 
+NEGATIVE_ENTRY = "the count matrix has a negative entry"      # the ValueError of every reader of a count matrix
+
+
+def to_plan_order(cell_of_row, *per_row):
+    """Host arrays with one entry per row of a presented matrix, scattered to plan order (row i is cell
+    ``cell_of_row[i]``); the arrays themselves when ``cell_of_row`` is None."""
+    if cell_of_row is None:
+        return per_row
+    out = tuple(np.empty_like(a) for a in per_row)
+    for o, a in zip(out, per_row):
+        o[cell_of_row] = a
+    return out
+
+
+class CountMatrix:
+    """A count input as the libraries that read the int32 matrix where it lies take it, checked in two steps.
+
+    ``CountMatrix(counts, who)`` accepts an int32 (cells, genes) torch tensor or a ``PresentedCounts`` and exposes ``X``,
+    ``N``, ``G`` and ``cell_of_row`` (None for a plain tensor); TypeError for anything but an int32 tensor, ValueError
+    for other than two dimensions.  ``who`` names the caller in the messages.  ``on_device()`` then requires a device
+    tensor with unit column stride and rows that do not overlap, sets ``ld`` (the row stride in elements) and ``device``
+    and returns the view.  Limits on N and G are the caller's, between the steps or after them."""
+
+    def __init__(self, counts, who):
+        torch = _torch()
+        self.who, self.cell_of_row = who, None
+        if isinstance(counts, PresentedCounts):
+            counts, self.cell_of_row = counts.counts, counts.cell_of_row
+        if not isinstance(counts, torch.Tensor):
+            raise TypeError("%s takes an int32 device tensor or a device.PresentedCounts, not %s (host arrays are refused: "
+                            "there is no CPU path)" % (who, type(counts).__name__))
+        if counts.dtype != torch.int32:
+            raise TypeError("%s needs int32 counts, not %s" % (who, counts.dtype))
+        if counts.dim() != 2:
+            raise ValueError("%s needs a (cells, genes) matrix, not %d dimensions" % (who, counts.dim()))
+        self.X = counts
+        self.N, self.G = counts.shape
+
+    def on_device(self):
+        X, N, G = self.X, self.N, self.G
+        if X.device.type != "cuda":
+            raise ValueError("%s needs a device tensor, not one on %s" % (self.who, X.device))
+        if G > 1 and X.stride(1) != 1:
+            raise ValueError("%s needs unit column stride (got %d)" % (self.who, X.stride(1)))
+        self.ld = X.stride(0) if N > 1 else G
+        if self.ld < G:
+            raise ValueError("rows overlap (row stride %d < %d genes)" % (self.ld, G))
+        self.device = X.device
+        return self
+
+    def stream(self):
+        """torch's current stream on the matrix's device, as the C ABI takes it."""
+        return ctypes.c_void_p(_torch().cuda.current_stream(self.device).cuda_stream)
+
+    def workspace(self, query, check, *sizes):
+        """A uint8 device tensor of the bytes that a library's ``*_workspace_bytes`` (``query``; ``check``: its
+        _native.check_*) asks for this matrix and ``sizes``."""
+        need = ctypes.c_uint64(0)
+        check(query(self.N, self.G, *sizes, ctypes.byref(need)))
+        return _torch().empty(max(int(need.value), 1), dtype=_torch().uint8, device=self.device)
+
+
 _contexts = {}
 
 

@@ -31,22 +31,17 @@ sum_j (S2_j - N mu_j^2) / (N - 1) of the per-gene sums S1, S2 of A and A^2 (bina
 
 There is no CPU fallback: host arrays are refused.
 """
-import ctypes
 from typing import NamedTuple
 
 import numpy as np
 
 from . import _native
 from . import device as _device
+from .device import _torch
 
 MAX_PANEL = 128                 # l: the widest panel the kernels take
 OVERSAMPLE = 10                 # l = min(k + OVERSAMPLE, N, G)
 MAX_COMPONENTS = MAX_PANEL - OVERSAMPLE
-
-
-def _torch():
-    import torch
-    return torch
 
 
 class PCA(NamedTuple):
@@ -61,24 +56,13 @@ class PCA(NamedTuple):
 
 
 def _counts(counts):
-    """(tensor, cell_of_row or None) of an accepted count input, checked up to (not including) its device."""
-    torch = _torch()
-    cell_of_row = None
-    if isinstance(counts, _device.PresentedCounts):
-        counts, cell_of_row = counts.counts, counts.cell_of_row
-    if not isinstance(counts, torch.Tensor):
-        raise TypeError("embed takes an int32 device tensor or a device.PresentedCounts, not %s (host arrays are not "
-                        "embedded here: there is no CPU path)" % type(counts).__name__)
-    if counts.dtype != torch.int32:
-        raise TypeError("embed needs int32 counts, not %s" % counts.dtype)
-    if counts.dim() != 2:
-        raise ValueError("embed needs a (cells, genes) matrix, not %d dimensions" % counts.dim())
-    N, G = counts.shape
-    if N < 1 or G < 1:
-        raise ValueError("embed needs at least one cell and one gene (got %d x %d)" % (N, G))
-    if N >= 1 << 31:
+    """The view (device.CountMatrix) of an accepted count input, checked up to (not including) its device."""
+    m = _device.CountMatrix(counts, "embed")
+    if m.N < 1 or m.G < 1:
+        raise ValueError("embed needs at least one cell and one gene (got %d x %d)" % (m.N, m.G))
+    if m.N >= 1 << 31:
         raise ValueError("embed takes fewer than 2^31 cells")
-    return counts, cell_of_row
+    return m
 
 
 def _inverse_sizes(size_factors, n_cells):
@@ -113,21 +97,15 @@ class LogNormalized:
 
     def __init__(self, counts, size_factors):
         torch = _torch()
-        X, cell_of_row = _counts(counts)
-        N, G = X.shape
+        m = _counts(counts)
+        N, cell_of_row = m.N, m.cell_of_row
         inv = _inverse_sizes(size_factors, N)
-        if X.device.type != "cuda":
-            raise ValueError("embed needs a device tensor, not one on %s" % X.device)
-        if G > 1 and X.stride(1) != 1:
-            raise ValueError("embed needs unit column stride (got %d)" % X.stride(1))
-        ld = X.stride(0) if N > 1 else G
-        if ld < G:
-            raise ValueError("rows overlap (row stride %d < %d genes)" % (ld, G))
+        self.matrix = m.on_device()
         _native.load_embed()
-        self.counts, self.ld, self.device, self.dtype = X, ld, X.device, torch.float32
+        X = m.X
+        self.counts, self.ld, self.device, self.dtype = X, m.ld, X.device, torch.float32
         self._row_of_cell = self._cell_of_row = None
         if cell_of_row is not None:
-            cell_of_row = np.asarray(cell_of_row, dtype=np.int64)
             row_of_cell = np.empty_like(cell_of_row)
             row_of_cell[cell_of_row] = np.arange(N, dtype=np.int64)
             inv = inv[cell_of_row]                                    # row i of X is cell cell_of_row[i]
@@ -140,19 +118,12 @@ class LogNormalized:
     def shape(self):
         return tuple(self.counts.shape)
 
-    def _stream(self):
-        return ctypes.c_void_p(_torch().cuda.current_stream(self.device).cuda_stream)
-
     def _workspace(self, l):
-        torch = _torch()
-        N, G = self.shape
-        need = ctypes.c_uint64(0)
-        _native.check_embed(_native.load_embed().prosstt_amd_embed_workspace_bytes(N, G, l, ctypes.byref(need)))
-        return torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
+        return self.matrix.workspace(_native.load_embed().prosstt_amd_embed_workspace_bytes, _native.check_embed, l)
 
     def _check_status(self):
         if int(self.status.item()):
-            raise ValueError("the count matrix has a negative entry")
+            raise ValueError(_device.NEGATIVE_ENTRY)
 
     def _panel(self, P, rows, name):
         torch = _torch()
@@ -178,8 +149,8 @@ class LogNormalized:
             ws = self._workspace(1)
             S = torch.empty(2, G, dtype=torch.float64, device=self.device)
             _native.check_embed(_native.load_embed().prosstt_amd_embed_gene_moments(
-                self._stream(), p(self.counts), N, G, self.ld, p(self.inv_size), p(ws), ws.numel(), p(S[0]), p(S[1]),
-                p(self.status)))
+                self.matrix.stream(), p(self.counts), N, G, self.ld, p(self.inv_size), p(ws), ws.numel(), p(S[0]),
+                p(S[1]), p(self.status)))
             self._check_status()
             S = S.cpu().numpy()
         return S[0].copy(), S[1].copy()
@@ -194,8 +165,8 @@ class LogNormalized:
             ws = self._workspace(l)
             Y = torch.empty(N, l, dtype=torch.float32, device=self.device)
             _native.check_embed(_native.load_embed().prosstt_amd_embed_matmul(
-                self._stream(), p(self.counts), N, G, self.ld, p(self.inv_size), p(W), l, p(Y), p(ws), ws.numel(),
-                p(self.status)))
+                self.matrix.stream(), p(self.counts), N, G, self.ld, p(self.inv_size), p(W), l, p(Y), p(ws),
+                ws.numel(), p(self.status)))
             self._check_status()
             if self._row_of_cell is not None:
                 Y = Y.index_select(0, self._row_of_cell)
@@ -213,8 +184,8 @@ class LogNormalized:
             ws = self._workspace(l)
             Z = torch.empty(G, l, dtype=torch.float32, device=self.device)
             _native.check_embed(_native.load_embed().prosstt_amd_embed_rmatmul(
-                self._stream(), p(self.counts), N, G, self.ld, p(self.inv_size), p(Q), l, p(Z), p(ws), ws.numel(),
-                p(self.status)))
+                self.matrix.stream(), p(self.counts), N, G, self.ld, p(self.inv_size), p(Q), l, p(Z), p(ws),
+                ws.numel(), p(self.status)))
             self._check_status()
         return Z
 
@@ -327,9 +298,8 @@ def pca(counts, size_factors, n_components=50, *, n_iter=7, seed=0):
     Raises TypeError for a host array or another dtype, ValueError for a CPU tensor, bad size factors, k or n_iter out of
     range, fewer than two cells, or a negative count."""
     torch = _torch()
-    X, _ = _counts(counts)
-    N, G = X.shape
-    k, n_iter = _check_components(N, G, n_components, n_iter)
+    m = _counts(counts)
+    k, n_iter = _check_components(m.N, m.G, n_components, n_iter)
     op = LogNormalized(counts, size_factors)
     with torch.cuda.device(op.device):
         S1, S2 = op.gene_moments()

@@ -16,20 +16,15 @@ matrix ever leaving the device.  Means and variances are formed from the exact i
 
 There is no CPU fallback: host arrays are refused.
 """
-import ctypes
 
 import numpy as np
 import pandas as pd
 
 from . import _native
 from . import device as _device
+from .device import _torch
 
 _U64 = 1 << 64
-
-
-def _torch():
-    import torch
-    return torch
 
 
 class CountSummary:
@@ -109,29 +104,11 @@ class CountSummary:
 
 
 def _matrix(counts):
-    """(device tensor, cell_of_row or None, ld) of an accepted input, or raise."""
-    torch = _torch()
-    cell_of_row = None
-    if isinstance(counts, _device.PresentedCounts):
-        counts, cell_of_row = counts.counts, counts.cell_of_row
-    if not isinstance(counts, torch.Tensor):
-        raise TypeError("count_summary takes an int32 device tensor or a device.PresentedCounts, not %s (host arrays are "
-                        "not summarised here: there is no CPU path)" % type(counts).__name__)
-    if counts.dtype != torch.int32:
-        raise TypeError("count_summary needs int32 counts, not %s" % counts.dtype)
-    if counts.device.type != "cuda":
-        raise ValueError("count_summary needs a device tensor, not one on %s" % counts.device)
-    if counts.dim() != 2:
-        raise ValueError("count_summary needs a (cells, genes) matrix, not %d dimensions" % counts.dim())
-    N, G = counts.shape
-    if N == 0:
+    """The checked device view (device.CountMatrix) of an accepted input, or raise."""
+    m = _device.CountMatrix(counts, "count_summary")
+    if m.N == 0:
         raise ValueError("count_summary needs at least one cell")
-    if G > 1 and counts.stride(1) != 1:
-        raise ValueError("count_summary needs unit column stride (got %d)" % counts.stride(1))
-    ld = counts.stride(0) if N > 1 else G
-    if ld < G:
-        raise ValueError("rows overlap (row stride %d < %d genes)" % (ld, G))
-    return counts, cell_of_row, ld
+    return m.on_device()
 
 
 class _Outputs:
@@ -147,17 +124,14 @@ class _Outputs:
         self.cell_zeros = torch.empty(n_cells, **z)
         self.status = torch.zeros(1, dtype=torch.int32, device=device)
 
-    def enqueue(self, X, ld, lo, accumulate):
-        """Summarise device matrix X into the gene outputs and cells [lo, lo + N) (on the current stream)."""
-        torch = _torch()
+    def enqueue(self, m, lo, accumulate):
+        """Summarise the device matrix of view m into the gene outputs and cells [lo, lo + N) (on the current stream)."""
         L = _native.load_stats()
-        N, G = X.shape
-        need = ctypes.c_uint64(0)
-        _native.check_stats(L.prosstt_amd_stats_workspace_bytes(N, G, ctypes.byref(need)))
-        ws = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=X.device)
+        N = m.N
+        ws = m.workspace(L.prosstt_amd_stats_workspace_bytes, _native.check_stats)
         p = _device._ptr
         _native.check_stats(L.prosstt_amd_stats_count_summary(
-            ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream), p(X), N, G, ld, p(ws), ws.numel(),
+            m.stream(), p(m.X), N, m.G, m.ld, p(ws), ws.numel(),
             p(self.gene_sum), p(self.gene_sumsq), p(self.gene_zeros), p(self.cell_total[lo:lo + N]),
             p(self.cell_zeros[lo:lo + N]), p(self.status), _native.STATS_ACCUMULATE if accumulate else 0))
 
@@ -168,7 +142,7 @@ class _Outputs:
                           self.cell_total, self.cell_zeros]).cpu().numpy()
         G, N = self.gene_sum.numel(), self.cell_total.numel()
         if flat[0]:
-            raise ValueError("the count matrix has a negative entry")
+            raise ValueError(_device.NEGATIVE_ENTRY)
         at = 1
         parts = []
         for n in (G, 2 * G, G, N, N):
@@ -189,17 +163,12 @@ def count_summary(counts):
     Raises TypeError for a host array or another dtype, ValueError for a CPU tensor, a non-unit column stride, no cells or
     a negative entry."""
     torch = _torch()
-    X, cell_of_row, ld = _matrix(counts)
-    with torch.cuda.device(X.device):
-        out = _Outputs(X.shape[0], X.shape[1], X.device)
-        out.enqueue(X, ld, 0, accumulate=False)
+    m = _matrix(counts)
+    with torch.cuda.device(m.device):
+        out = _Outputs(m.N, m.G, m.device)
+        out.enqueue(m, 0, accumulate=False)
         gene_sum, sumsq, gene_zeros, cell_total, cell_zeros = out.fetch()
-    if cell_of_row is not None:                  # row i of the device matrix is cell cell_of_row[i]
-        total, zeros = np.empty_like(cell_total), np.empty_like(cell_zeros)
-        total[cell_of_row] = cell_total
-        zeros[cell_of_row] = cell_zeros
-        cell_total, cell_zeros = total, zeros
-    return CountSummary(gene_sum, sumsq, gene_zeros, cell_total, cell_zeros)
+    return CountSummary(gene_sum, sumsq, gene_zeros, *_device.to_plan_order(m.cell_of_row, cell_total, cell_zeros))
 
 
 def default_chunk_cells(no_cells, G):
@@ -228,17 +197,14 @@ def sample_density_summary(tree, no_cells, alpha=0.3, beta=2, scale=True, scale_
     lo = 0
     for part, pt, br, sc in sim.sample_density_chunks(tree, no_cells, chunk_cells, alpha, beta, scale, scale_v, scale_mean,
                                                       seed=seed, out="torch", strict=strict):
-        X, cell_of_row, ld = _matrix(part)
-        out.enqueue(X, ld, lo, accumulate=True)
-        perms.append(lo + cell_of_row)
+        m = _matrix(part)
+        out.enqueue(m, lo, accumulate=True)
+        perms.append(lo + m.cell_of_row)
         pts.append(pt)
         brs.append(br)
         scs.append(sc)
-        lo += X.shape[0]
+        lo += m.N
     gene_sum, sumsq, gene_zeros, cell_total, cell_zeros = out.fetch()
-    cell_of_row = np.concatenate(perms)
-    total, zeros = np.empty_like(cell_total), np.empty_like(cell_zeros)
-    total[cell_of_row] = cell_total
-    zeros[cell_of_row] = cell_zeros
+    total, zeros = _device.to_plan_order(np.concatenate(perms), cell_total, cell_zeros)
     return (CountSummary(gene_sum, sumsq, gene_zeros, total, zeros), np.concatenate(pts), np.concatenate(brs),
             np.concatenate(scs))

@@ -1,11 +1,17 @@
 """embed.pca's driver (prosstt_amd/embed.py: _randomized_pca) on a binary64 torch-CPU stand-in for the device operator,
 against the exact SVD of the centred log1p(X / s); and the argument checks that refuse before any device use."""
+import ctypes
+import os
+import re
+
 import numpy as np
 import pytest
 
+from conftest import ROOT
+
 torch = pytest.importorskip("torch")
 
-from prosstt_amd import embed  # noqa: E402
+from prosstt_amd import _native, device, embed  # noqa: E402
 
 
 def synthetic(seed=20261016, N=3000, G=1500, rank=8):
@@ -158,6 +164,40 @@ def test_host_arrays_are_refused():
         embed.pca(torch.as_tensor(X), s, 5)                   # a CPU tensor
     with pytest.raises(ValueError, match="device"):
         embed.LogNormalized(torch.as_tensor(X), s)
+
+
+def test_count_matrix_view_refusals():
+    """device.CountMatrix, the checked view behind embed and summary: step 1 on any input, step 2 (on_device) after it."""
+    X, _ = synthetic(N=20, G=10)
+    with pytest.raises(TypeError, match="no CPU path"):
+        device.CountMatrix(X, "caller")                                   # a host array
+    with pytest.raises(TypeError, match="int32"):
+        device.CountMatrix(torch.as_tensor(X, dtype=torch.int64), "caller")
+    with pytest.raises(ValueError, match="dimensions"):
+        device.CountMatrix(torch.as_tensor(X).reshape(4, 5, 10), "caller")
+    with pytest.raises(TypeError):
+        device.CountMatrix(device.PresentedCounts(X, np.arange(20)), "caller")
+    order = np.arange(20)[::-1]
+    for given, cell_of_row in ((torch.as_tensor(X), None), (device.PresentedCounts(torch.as_tensor(X), order), order)):
+        m = device.CountMatrix(given, "caller")                           # step 1 accepts a CPU tensor
+        assert (m.N, m.G) == (20, 10) and m.X.dtype == torch.int32
+        assert m.cell_of_row is None if cell_of_row is None else np.array_equal(m.cell_of_row, cell_of_row)
+        with pytest.raises(ValueError, match="caller needs a device tensor"):
+            m.on_device()
+    total = np.arange(20)
+    assert device.to_plan_order(None, total)[0] is total
+    got, = device.to_plan_order(order, total)
+    assert np.array_equal(got, total[::-1]) and got is not total
+
+
+def test_library_exports_every_declared_symbol():
+    header = open(os.path.join(ROOT, "include", "prosstt_amd_embed.h")).read()
+    declared = set(re.findall(r"\b(prosstt_amd_embed_[a-z_0-9]+)\s*\(", header))
+    assert declared == set(_native.EMBED_SYMBOLS)
+    if os.path.exists(_native.EMBED_LIB_PATH):
+        lib = ctypes.CDLL(_native.EMBED_LIB_PATH)
+        for name in declared:
+            assert hasattr(lib, name), name
 
 
 @pytest.mark.parametrize("bad", ["short", "zero", "negative", "nan", "inf", "tiny"])

@@ -10,7 +10,6 @@ Times of the PCA passes (prosstt_amd/embed.py, libprosstt_amd_embed.so) on the d
     python tools/embed_bench.py [--configs C3,T32] [--reps 20] [--l 64] [--sklearn]
 """
 import argparse
-import ctypes
 import os
 import sys
 import time
@@ -27,15 +26,13 @@ def kernel_times(op, l, reps):
     L = _native.load_embed()
     p = device._ptr
     N, G = op.shape
-    need = ctypes.c_uint64(0)
-    _native.check_embed(L.prosstt_amd_embed_workspace_bytes(N, G, l, ctypes.byref(need)))
-    ws = torch.empty(int(need.value), dtype=torch.uint8, device=op.device)
+    ws = op.matrix.workspace(L.prosstt_amd_embed_workspace_bytes, _native.check_embed, l)
     W = torch.randn(G, l, device=op.device)
     Q = torch.randn(N, l, device=op.device)
     Y = torch.empty(N, l, device=op.device)
     Z = torch.empty(G, l, device=op.device)
     S = torch.empty(2, G, dtype=torch.float64, device=op.device)
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = op.matrix.stream()
     X, ld, inv, status = p(op.counts), op.ld, p(op.inv_size), p(op.status)
     calls = {
         "gene_moments": lambda: L.prosstt_amd_embed_gene_moments(st, X, N, G, ld, inv, p(ws), ws.numel(), p(S[0]), p(S[1]),

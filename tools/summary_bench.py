@@ -20,15 +20,26 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def kernel_time(X, reps):
     import torch
-    from prosstt_amd import summary
-    X, _, ld = summary._matrix(X)
-    out = summary._Outputs(X.shape[0], X.shape[1], X.device)
+    from prosstt_amd import _native, device
+    L = _native.load_stats()
+    p = device._ptr
+    m = device.CountMatrix(X, "summary_bench").on_device()
+    genes = torch.zeros(4, m.G, dtype=torch.int64, device=m.device)          # sum, sumsq (low, high), zeros
+    cells = torch.empty(2, m.N, dtype=torch.int64, device=m.device)
+    status = torch.zeros(1, dtype=torch.int32, device=m.device)
+
+    def enqueue():                                       # what summary.count_summary enqueues, workspace included
+        ws = m.workspace(L.prosstt_amd_stats_workspace_bytes, _native.check_stats)
+        _native.check_stats(L.prosstt_amd_stats_count_summary(
+            m.stream(), p(m.X), m.N, m.G, m.ld, p(ws), ws.numel(), p(genes[0]), p(genes[1:3]), p(genes[3]), p(cells[0]),
+            p(cells[1]), p(status), 0))
+
     for _ in range(3):
-        out.enqueue(X, ld, 0, accumulate=False)
+        enqueue()
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     start.record()
     for _ in range(reps):
-        out.enqueue(X, ld, 0, accumulate=False)
+        enqueue()
     stop.record()
     stop.synchronize()
     return start.elapsed_time(stop) / reps
