@@ -13,9 +13,19 @@
 //                           K2a: max(programs@H) and per-sibling anticorrelated-gene
 //                           counts without materialising (T,G)   (simulation.py:269-272)
 //   lineage_commit_kernel   K2b: rel = programs@H in binary64 + per-gene max
+//   gene_max_kernel         per-gene max of rows of rel that are on the device already
+//                           (GeneColumn is the product programs@H of all three K2 kernels: where a gene's column of H sits
+//                           and the order of the fma chain; fold_gene_max is the end of K2b and gene_max_kernel)
 //   lineage_walk_kernel     K1: device-mode expression programs (simulation.py:89-124)
 //   means_from_rel_kernel   Tree.add_genes: exp(rel)*base -> binary32 mean tensor (tree.py:181-182)
 // Host only: prosstt_amd_numpy_programs (numpy_stream.h): numpy's legacy stream for a batch of attempts.
+//
+// Host side, each decision in one place
+//   ScratchWord             the words of the ctx's device scratch
+//   Staging                 a call's arrays that may be host pointers (PROSSTT_AMD_HOST_INPUTS / _OUTPUT)
+//   stream_geometry         launch geometry and list capacities of a sample_counts call
+//   stream_workspace        the regions of its workspace: their sizes and their addresses
+//   sampler_setup           the common front end of sample_counts and nb_params
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -68,7 +78,7 @@ struct prosstt_amd_ctx {
     hipStream_t stream = nullptr;
     void* ws = nullptr;          // grow-only device workspace
     size_t ws_bytes = 0;
-    int64_t* scratch = nullptr;  // device: [0] domain flag, [1] max bits, [2..] counters
+    int64_t* scratch = nullptr;  // device: kScratchWords words (ScratchWord below)
     int64_t* h_scratch = nullptr;  // pinned mirror
     std::vector<hipEvent_t> events;  // (start, stop) pairs of kernels launched with TIME_KERNEL
     size_t events_used = 0;
@@ -83,7 +93,7 @@ struct prosstt_amd_ctx {
     const float* row_bad_means = nullptr;
     int64_t row_bad_rows = 0;
     int32_t row_bad_G = 0;
-    uint32_t call_parity = 0;    // the full-test request word of a call is scratch[6 + parity]; a call clears the other one
+    uint32_t call_parity = 0;    // the full-test request word of a call is scratch[kFullReq + parity]; a call clears the other one
 };
 
 // next (start, stop) event pair of the ctx's pool
@@ -101,11 +111,16 @@ static int next_event_pair(prosstt_amd_ctx* c, hipEvent_t* a, hipEvent_t* b)
     c->events_used += 2;
     return 0;
 }
-// scratch words: [3] list overflow of the last sample_counts call; [4] sticky "domain error", [5] sticky "row index outside
-// the tensor" (both set by checked calls, read and cleared by prosstt_amd_domain_status); [6], [7] "some gene has alpha < 0 or
-// beta < 1: run the full test" of calls of even / odd parity
-constexpr int kScratchWords = 128 + 32 * 16;
-constexpr int kStickyDomain = 4, kStickyRow = 5, kFullReq = 6;
+// The words of prosstt_amd_ctx::scratch (zero at creation; words 0 to 2 are not used).
+enum ScratchWord : int {
+    kListOverflow = 3,   // some region of the last sample_counts call's list was too small (k3::HeavyList::overflow: cleared
+                         // by the preparation kernel, set by the streaming kernel, read by prosstt_amd_last_list)
+    kStickyDomain = 4,   // "domain error" and ...
+    kStickyRow = 5,      // ... "row index outside the tensor": set by checked calls, read and cleared together (domain_verdict)
+    kFullReq = 6,        // [kFullReq + parity]: "some gene has alpha < 0 or beta < 1: run the full test" of calls of even / odd parity
+    kScratchWords = 8
+};
+static_assert(kStickyRow == kStickyDomain + 1, "domain_verdict copies and clears the two sticky words as one 16-byte range");
 
 static int ws_reserve(prosstt_amd_ctx* c, size_t bytes)
 {
@@ -124,9 +139,12 @@ static int ws_reserve(prosstt_amd_ctx* c, size_t bytes)
     return 0;
 }
 
-// Temporary device copies of host arrays (PROSSTT_AMD_HOST_INPUTS / _OUTPUT).
+// Temporary device copies of a call's host arrays: with PROSSTT_AMD_HOST_INPUTS / _OUTPUT among the call's flags its input /
+// output pointers are host pointers.  All copies are asynchronous on the call's stream; the call synchronises before it returns.
 struct Staging {
+    const bool host_in, host_out;
     std::vector<void*> bufs;
+    explicit Staging(uint32_t flags = 0) : host_in(flags & PROSSTT_AMD_HOST_INPUTS), host_out(flags & PROSSTT_AMD_HOST_OUTPUT) {}
     ~Staging() { for (void* p : bufs) (void)hipFree(p); }
     int alloc(void** p, size_t bytes)
     {
@@ -134,13 +152,31 @@ struct Staging {
         bufs.push_back(*p);
         return 0;
     }
-    int upload(const void* host, size_t bytes, const void** dev, hipStream_t s)
+    // an input of `count` elements: a host pointer is replaced by its device copy (an absent array stays absent)
+    template <class T> int in(const T*& p, size_t count, hipStream_t s)
     {
-        void* p = nullptr;
-        int rc = alloc(&p, bytes);
+        if (!host_in || !p) return 0;
+        void* d = nullptr;
+        int rc = alloc(&d, count * sizeof(T));
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, s));
-        *dev = p;
+        HIP_TRY(hipMemcpyAsync(d, p, count * sizeof(T), hipMemcpyHostToDevice, s));
+        p = (const T*)d;
+        return 0;
+    }
+    // an output of `count` elements: a host pointer is replaced by a device buffer for the kernel to write ...
+    template <class T> int out(T*& p, size_t count)
+    {
+        if (!host_out || !p) return 0;
+        void* d = nullptr;
+        int rc = alloc(&d, count * sizeof(T));
+        if (rc) return rc;
+        p = (T*)d;
+        return 0;
+    }
+    // ... which travels back behind the kernel
+    template <class T> int back(T* host, const T* dev, size_t count, hipStream_t s)
+    {
+        if (host_out && host) HIP_TRY(hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, s));
         return 0;
     }
 };
@@ -163,7 +199,7 @@ __global__ void prep_kernel(const double* __restrict__ scaling, int64_t N,
                             float* __restrict__ scal_f, float* __restrict__ a_f,
                             float* __restrict__ bm1_f, float* __restrict__ phi_f,
                             const int32_t* __restrict__ row_of_cell, int64_t rows, uint64_t cell_offset,
-                            const int64_t* __restrict__ cell_index, int32_t strip_cells,
+                            const int64_t* __restrict__ cell_index,
                             uint32_t k0, uint32_t k1, k3::CellInfo* __restrict__ info, int64_t* __restrict__ flags,
                             const uint8_t* __restrict__ row_bad, uint32_t parity, k3::HeavyList heavy,
                             k3::HeavyList* __restrict__ heavy_rec)
@@ -172,7 +208,7 @@ __global__ void prep_kernel(const double* __restrict__ scaling, int64_t N,
     if (heavy_rec && i < k3::kSegs + 2) heavy.seg_cnt[i] = 0u;      // the fill of the dense lists K3h reads
     if (heavy_rec && i == 0) *heavy_rec = heavy;                       // ... and their description, for the two kernels behind
     if (flags && i == 0) {
-        flags[3] = 0;                       // list overflow of this call (set by the streaming kernel)
+        flags[kListOverflow] = 0;           // of this call (set by the streaming kernel)
         flags[kFullReq + (parity ^ 1u)] = 0;  // the NEXT call's full-test request (this call's was cleared by the previous one)
     }
     if (i < N) {
@@ -281,6 +317,52 @@ static double from_ordered_bits(unsigned long long o)
 // column of a gene sits in registers when K <= 32); the chunks' partial sums meet in LDS.
 constexpr int kLinChunks = 4;
 
+// The lineage product x = sum_k P[k] * H[k][g] of one gene g and one row P of a program matrix: by fma over k in ascending
+// order from 0.0 -- the order that tests/test_gpu_lineage_paths.py pins bit for bit to the binary64 model, written here and
+// nowhere else.  HREG (K <= 32): the gene's column of H sits in 32 registers, zero beyond K; else it is read from global
+// memory at every product.  A gene beyond G (`live` false) takes column 0: its products are computed and never used.
+template <bool HREG>
+struct GeneColumn {
+    const double* h;
+    int64_t G;
+    int32_t K;
+    double reg[HREG ? 32 : 1];
+    __device__ __forceinline__ GeneColumn(const double* H, int64_t g, bool live, int64_t G_, int32_t K_) : h(H + (live ? g : 0)), G(G_), K(K_)
+    {
+        if (HREG) {
+#pragma unroll
+            for (int k = 0; k < 32; ++k) reg[k] = k < K ? h[(int64_t)k * G] : 0.0;
+        }
+    }
+    __device__ __forceinline__ double dot(const double* row) const
+    {
+        double acc = 0.0;
+        if (HREG) {
+#pragma unroll
+            for (int k = 0; k < 32; ++k)
+                if (k < K) acc = fma(row[k], reg[k], acc);
+        } else {
+            for (int k = 0; k < K; ++k) acc = fma(row[k], h[(int64_t)k * G], acc);
+        }
+        return acc;
+    }
+    // two genes against one row: one read of a program entry feeds both chains (the LDS kernel's ratio of reads to FMAs)
+    static __device__ __forceinline__ void dot2(const GeneColumn& a, const GeneColumn& b, const double* row, double& x0, double& x1)
+    {
+        static_assert(HREG, "two columns at once only from registers");
+        double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int k = 0; k < 32; ++k)
+            if (k < a.K) {
+                const double p = row[k];
+                s0 = fma(p, a.reg[k], s0);
+                s1 = fma(p, b.reg[k], s1);
+            }
+        x0 = s0;
+        x1 = s1;
+    }
+};
+
 template <bool HREG>
 __global__ __launch_bounds__(256) void lineage_attempt_kernel(
     const double* __restrict__ progs, const int32_t* __restrict__ meta, int32_t T, int32_t K,
@@ -295,27 +377,11 @@ __global__ __launch_bounds__(256) void lineage_attempt_kernel(
     const int gl = threadIdx.x & 63, c = threadIdx.x >> 6;
     const int64_t g = (int64_t)blockIdx.x * 64 + gl;
     const bool live = g < G;
-    const double* h = H + (live ? g : 0);
     const int n_sib = meta[0];
-    double hreg[HREG ? 32 : 1];
-    if (HREG) {
-#pragma unroll
-        for (int k = 0; k < 32; ++k) hreg[k] = k < K ? h[(int64_t)k * G] : 0.0;
-    }
-    auto dot = [&](const double* row) -> double {
-        double acc = 0.0;
-        if (HREG) {
-#pragma unroll
-            for (int k = 0; k < 32; ++k)
-                if (k < K) acc = fma(row[k], hreg[k], acc);
-        } else {
-            for (int k = 0; k < K; ++k) acc = fma(row[k], h[(int64_t)k * G], acc);
-        }
-        return acc;
-    };
+    const GeneColumn<HREG> col(H, g, live, G, K);
 
     double mx = -std::numeric_limits<double>::infinity();
-    for (int t = (c * T) / kLinChunks; t < ((c + 1) * T) / kLinChunks; ++t) mx = fmax(mx, dot(progs + (int64_t)t * K));
+    for (int t = (c * T) / kLinChunks; t < ((c + 1) * T) / kLinChunks; ++t) mx = fmax(mx, col.dot(progs + (int64_t)t * K));
     if (!live) mx = -std::numeric_limits<double>::infinity();
     for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
     if (gl == 0) atomicMax(max_bits, ordered_bits(mx));
@@ -328,7 +394,7 @@ __global__ __launch_bounds__(256) void lineage_attempt_kernel(
         blk += 2 * (int64_t)common * K;
         double cov = 0.0, vx = 0.0, vy = 0.0;
         for (int t = (c * common) / kLinChunks; t < ((c + 1) * common) / kLinChunks; ++t) {
-            const double x = dot(pc + (int64_t)t * K), y = dot(ps + (int64_t)t * K);
+            const double x = col.dot(pc + (int64_t)t * K), y = col.dot(ps + (int64_t)t * K);
             cov = fma(x, y, cov);
             vx = fma(x, x, vx);
             vy = fma(y, y, vy);
@@ -368,27 +434,8 @@ __global__ __launch_bounds__(256) void lineage_attempt_lds_kernel(
     const int gl = threadIdx.x & 63, c = threadIdx.x >> 6;
     const int64_t g0 = (int64_t)blockIdx.x * kAttGenes + gl, g1 = g0 + 64;
     const bool live0 = g0 < G, live1 = g1 < G;
-    const double* h0 = H + (live0 ? g0 : 0);
-    const double* h1 = H + (live1 ? g1 : 0);
     const int n_sib = meta[0];
-    double a0[32], a1[32];
-#pragma unroll
-    for (int k = 0; k < 32; ++k) {
-        a0[k] = k < K ? h0[(int64_t)k * G] : 0.0;
-        a1[k] = k < K ? h1[(int64_t)k * G] : 0.0;
-    }
-    auto dot2 = [&](const double* row, double& x0, double& x1) {
-        double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-        for (int k = 0; k < 32; ++k)
-            if (k < K) {
-                const double p = row[k];
-                s0 = fma(p, a0[k], s0);
-                s1 = fma(p, a1[k], s1);
-            }
-        x0 = s0;
-        x1 = s1;
-    };
+    const GeneColumn<true> col0(H, g0, live0, G, K), col1(H, g1, live1, G, K);
     auto stage = [&](const double* src, int doubles) {
         __syncthreads();                               // (the previous phase has finished with buf)
         for (int i = threadIdx.x; i < doubles; i += 256) buf[i] = src[i];
@@ -399,7 +446,7 @@ __global__ __launch_bounds__(256) void lineage_attempt_lds_kernel(
     double mx = -std::numeric_limits<double>::infinity();
     for (int t = (c * T) / kLinChunks; t < ((c + 1) * T) / kLinChunks; ++t) {
         double x0, x1;
-        dot2(buf + t * K, x0, x1);
+        GeneColumn<true>::dot2(col0, col1, buf + t * K, x0, x1);
         if (live0) mx = fmax(mx, x0);
         if (live1) mx = fmax(mx, x1);
     }
@@ -416,8 +463,8 @@ __global__ __launch_bounds__(256) void lineage_attempt_lds_kernel(
         double cov0 = 0.0, vx0 = 0.0, vy0 = 0.0, cov1 = 0.0, vx1 = 0.0, vy1 = 0.0;
         for (int t = (c * common) / kLinChunks; t < ((c + 1) * common) / kLinChunks; ++t) {
             double x0, x1, y0, y1;
-            dot2(pc + t * K, x0, x1);
-            dot2(ps + t * K, y0, y1);
+            GeneColumn<true>::dot2(col0, col1, pc + t * K, x0, x1);
+            GeneColumn<true>::dot2(col0, col1, ps + t * K, y0, y1);
             cov0 = fma(x0, y0, cov0); vx0 = fma(x0, x0, vx0); vy0 = fma(y0, y0, vy0);
             cov1 = fma(x1, y1, cov1); vx1 = fma(x1, x1, vx1); vy1 = fma(y1, y1, vy1);
         }
@@ -475,6 +522,17 @@ __device__ __forceinline__ void atomic_max_f64(double* cell, double v)
     }
 }
 
+// The end of a block of 64 genes x 4 waves, every thread with its partial maximum `mx` of gene g (every thread of the block
+// arrives): the four meet in LDS and wave 0 folds them into gene_max[g].
+__device__ __forceinline__ void fold_gene_max(double mx, bool live, double* __restrict__ gene_max, int64_t g)
+{
+    __shared__ double part[4][64];
+    const int gl = threadIdx.x & 63, c = threadIdx.x >> 6;
+    part[c][gl] = mx;
+    __syncthreads();
+    if (c == 0 && live) atomic_max_f64(&gene_max[g], fmax(fmax(part[0][gl], part[1][gl]), fmax(part[2][gl], part[3][gl])));
+}
+
 // K2b: rel[t][g] = sum_k progs[t][k] * H[k][g] for an accepted branch, and its per-gene maximum folded into gene_max.
 // Block = 64 genes x 4 groups of time steps, blockIdx.y = one of gridDim.y ranges of the T steps (the host picks them
 // so that the launch has >= 1024 blocks); the range's programs sit in LDS (wave-uniform reads), a gene's H column in
@@ -489,53 +547,33 @@ __global__ __launch_bounds__(256) void lineage_commit_kernel(const double* __res
                                                              double* __restrict__ gene_max)
 {
     __shared__ double pl[kCommitLdsDoubles];
-    __shared__ double part[4][64];
     const int gl = threadIdx.x & 63, c = threadIdx.x >> 6;
     const int64_t g = (int64_t)blockIdx.x * 64 + gl;
     const bool live = g < G;
     const int t0 = (int)(((int64_t)blockIdx.y * T) / gridDim.y), t1 = (int)(((int64_t)(blockIdx.y + 1) * T) / gridDim.y);
     for (int i = threadIdx.x; i < (t1 - t0) * K; i += 256) pl[i] = progs[(int64_t)t0 * K + i];
-    const double* h = H + (live ? g : 0);
-    double hreg[HREG ? 32 : 1];
-    if (HREG) {
-#pragma unroll
-        for (int k = 0; k < 32; ++k) hreg[k] = k < K ? h[(int64_t)k * G] : 0.0;
-    }
+    const GeneColumn<HREG> col(H, g, live, G, K);
     __syncthreads();
     double mx = -std::numeric_limits<double>::infinity();
     for (int t = t0 + c; t < t1; t += 4) {
-        const double* row = pl + (t - t0) * K;
-        double acc = 0.0;
-        if (HREG) {
-#pragma unroll
-            for (int k = 0; k < 32; ++k)
-                if (k < K) acc = fma(row[k], hreg[k], acc);
-        } else {
-            for (int k = 0; k < K; ++k) acc = fma(row[k], h[(int64_t)k * G], acc);
-        }
+        const double acc = col.dot(pl + (t - t0) * K);
         if (live && rel_out) rel_out[(int64_t)t * G + g] = acc;
         mx = fmax(mx, acc);
     }
-    if (!gene_max) return;
-    part[c][gl] = mx;
-    __syncthreads();
-    if (c == 0 && live) atomic_max_f64(&gene_max[g], fmax(fmax(part[0][gl], part[1][gl]), fmax(part[2][gl], part[3][gl])));
+    if (gene_max) fold_gene_max(mx, live, gene_max, g);
 }
 
 // gene_max[g] = max(gene_max[g], max over rows of rel[row][g]): block = 64 genes x 4 groups of rows, blockIdx.y = a range of rows
 __global__ __launch_bounds__(256) void gene_max_kernel(const double* __restrict__ rel, int64_t rows,
                                                        int64_t G, double* __restrict__ gene_max)
 {
-    __shared__ double part[4][64];
-    const int gl = threadIdx.x & 63, c = threadIdx.x >> 6;
-    const int64_t g = (int64_t)blockIdx.x * 64 + gl;
+    const int c = threadIdx.x >> 6;
+    const int64_t g = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
     const int64_t r0 = ((int64_t)blockIdx.y * rows) / gridDim.y, r1 = ((int64_t)(blockIdx.y + 1) * rows) / gridDim.y;
     double mx = -std::numeric_limits<double>::infinity();
     if (g < G)
         for (int64_t t = r0 + c; t < r1; t += 4) mx = fmax(mx, rel[t * G + g]);
-    part[c][gl] = mx;
-    __syncthreads();
-    if (c == 0 && g < G) atomic_max_f64(&gene_max[g], fmax(fmax(part[0][gl], part[1][gl]), fmax(part[2][gl], part[3][gl])));
+    fold_gene_max(mx, g < G, gene_max, g);
 }
 
 __global__ __launch_bounds__(256) void means_from_rel_kernel(const double* __restrict__ rel,
@@ -674,7 +712,6 @@ struct SamplerArgs {
     const float* means; const int32_t* row_of_cell;
     const int64_t* cell_index;   // device copy (NULL: cells are numbered from cell_offset)
     float *scal, *ga, *gbm1, *gphi;
-    void* extra;     // `extra_bytes` of workspace behind the parameter vectors (256-B aligned)
     k3::HeavyList heavy;           // K3h's lists (a sample_counts call) ...
     k3::HeavyList* heavy_rec;      // ... and where the preparation kernel puts their description for the kernels behind it
     k3::CellInfo* cellinfo;
@@ -688,11 +725,9 @@ struct StreamGeometry {
     uint64_t regions;       // one region of the K3h list per wave
     uint32_t region_cap;    // room for one in 16 of a wave's samples (beyond that K3h redoes the region itself)
     uint32_t ent_cap;          // entries per segment of the dense lists K3h reads (k3::HeavyList)
-    size_t list_bytes, cnt_bytes, dense_bytes, count_bytes, ent_bytes, wst_bytes, wid_bytes, ovf_bytes, redo_bytes, info_bytes;
-    size_t total() const { return list_bytes + cnt_bytes + dense_bytes + count_bytes + ent_bytes + wst_bytes + wid_bytes + ovf_bytes + redo_bytes + info_bytes + 256; }
 };
 
-static StreamGeometry stream_geometry(int64_t N, int32_t G, int64_t rows)
+static StreamGeometry stream_geometry(int64_t N, int32_t G)
 {
     StreamGeometry g;
     g.tiles_g = ((int64_t)(G > 0 ? G : 0) + kTileG - 1) / kTileG;
@@ -704,24 +739,48 @@ static StreamGeometry stream_geometry(int64_t N, int32_t G, int64_t rows)
     g.regions = (uint64_t)(g.groups * g.tiles_g) * 4u;
     g.region_cap = (uint32_t)g.strip_cells * (kTileG / 16);
     if (g.region_cap > 1024u) g.region_cap = 1024u;             // K3h's second phase takes kDense + 16 chunks of 64
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    g.list_bytes = pad(g.regions * ((size_t)g.region_cap + k3::kListTail) * sizeof(uint2));      // staging: {pos, scaled mean} per region (+ its tail)
-    g.cnt_bytes = pad(768 + sizeof(k3::HeavyList));      // the segments' counters, and (at 768) the lists' description
-    static_assert((k3::kSegs + 2) * 4 <= 768, "the counters end where the record starts");
-    g.dense_bytes = pad(g.regions * (size_t)k3::kDense * sizeof(uint2));      // a region's first entries
-    g.count_bytes = pad(g.regions * 4u);
     // the segments (what regions list beyond their first kDense entries) take one sample in 64 of the matrix between them
     // (typical workloads list one to three in a thousand); a region that finds its segment full is redone as a whole, like
     // one whose own list was too small
     const uint64_t per_seg = ((uint64_t)n * (uint64_t)(G > 0 ? G : 0) / 64u + k3::kSegs - 1) / k3::kSegs;
     g.ent_cap = (uint32_t)(per_seg < 4u * g.region_cap ? 4u * g.region_cap : (per_seg > 0x7fffffffull ? 0x7fffffffull : per_seg));
-    g.ent_bytes = pad((size_t)k3::kSegs * g.ent_cap * sizeof(k3::HeavyEntry));
-    g.wst_bytes = pad(g.regions * (size_t)k3::kWalkSlots * 16u);            // walk states handed over
-    g.wid_bytes = pad(g.regions * (size_t)k3::kWalkSlots * 4u);
-    g.ovf_bytes = pad(g.regions * 4u);
-    g.redo_bytes = pad((size_t)k3::kRedoCap * sizeof(int2));
-    g.info_bytes = ((size_t)n + 4) * sizeof(k3::CellInfo);
     return g;
+}
+
+// What a sample_counts call keeps in the workspace behind the parameter vectors: the one description of its regions, in
+// their order.  Walked with `base` NULL it sizes them (`bytes`; the pointers stay NULL), with the workspace's address it
+// places them.  Every region starts on a multiple of 256 bytes.
+struct StreamWorkspace {
+    k3::HeavyList heavy;         // (cap, ent_cap and overflow are the caller's to fill)
+    k3::HeavyList* heavy_rec;
+    k3::CellInfo* info;
+    size_t bytes;
+};
+
+static StreamWorkspace stream_workspace(const StreamGeometry& g, int64_t N, char* base)
+{
+    size_t at = 0;
+    auto take = [&](size_t bytes) {
+        char* p = base ? base + at : nullptr;
+        at += (bytes + 255) & ~(size_t)255;
+        return p;
+    };
+    StreamWorkspace w{};
+    w.heavy.list = (uint2*)take(g.regions * ((size_t)g.region_cap + k3::kListTail) * sizeof(uint2));   // staging: {pos, scaled mean} per region (+ its tail)
+    char* counters = take(768 + sizeof(k3::HeavyList));      // the segments' counters (zeroed by the preparation kernel), and at 768 the lists' description
+    static_assert((k3::kSegs + 2) * 4 <= 768, "the counters end where the record starts");
+    w.heavy.seg_cnt = (uint32_t*)counters;
+    w.heavy_rec = (k3::HeavyList*)(counters ? counters + 768 : nullptr);
+    w.heavy.dense = (uint2*)take(g.regions * (size_t)k3::kDense * sizeof(uint2));      // a region's first entries
+    w.heavy.count = (uint32_t*)take(g.regions * 4u);
+    w.heavy.ent = (k3::HeavyEntry*)take((size_t)k3::kSegs * g.ent_cap * sizeof(k3::HeavyEntry));
+    w.heavy.wst = (k3::f32x4_t*)take(g.regions * (size_t)k3::kWalkSlots * 16u);            // walk states handed over
+    w.heavy.wid = (uint32_t*)take(g.regions * (size_t)k3::kWalkSlots * 4u);
+    w.heavy.ovf_regions = (uint32_t*)take(g.regions * 4u);
+    w.heavy.redo = (int2*)take((size_t)k3::kRedoCap * sizeof(int2));
+    w.info = (k3::CellInfo*)take(0);
+    w.bytes = at + ((size_t)N + 4) * sizeof(k3::CellInfo) + 256;      // the cell records are the last region: not padded, 256 bytes of slack behind them
+    return w;
 }
 
 static int sampler_setup(prosstt_amd_ctx* c, Staging& st, const float* means, int64_t rows, int32_t G,
@@ -737,33 +796,19 @@ static int sampler_setup(prosstt_amd_ctx* c, Staging& st, const float* means, in
     if ((int64_t)G * 4 > (int64_t)1 << 33) return fail(PROSSTT_AMD_EINVAL, "G too large");
     HIP_TRY(hipSetDevice(c->device));
     if (N == 0 || G == 0) return 0;
-    if (flags & PROSSTT_AMD_HOST_INPUTS) {
-        // host-side bounds check is free here; device pointers are the caller's contract
+    if (st.host_in)   // host-side bounds check is free here; device pointers are the caller's contract
         for (int64_t n = 0; n < N; ++n)
             if (row_of_cell[n] < 0 || row_of_cell[n] >= rows)
                 return fail(PROSSTT_AMD_EINVAL, "row_of_cell[%lld] = %d outside [0,%lld)", (long long)n,
                             row_of_cell[n], (long long)rows);
-        int rc;
-        const void* d;
-        if ((rc = st.upload(means, (size_t)rows * G * 4, &d, c->stream))) return rc;
-        means = (const float*)d;
-        if ((rc = st.upload(row_of_cell, (size_t)N * 4, &d, c->stream))) return rc;
-        row_of_cell = (const int32_t*)d;
-        if ((rc = st.upload(scaling, (size_t)N * 8, &d, c->stream))) return rc;
-        scaling = (const double*)d;
-        if ((rc = st.upload(alpha, (size_t)G * 8, &d, c->stream))) return rc;
-        alpha = (const double*)d;
-        if ((rc = st.upload(beta, (size_t)G * 8, &d, c->stream))) return rc;
-        beta = (const double*)d;
-        if (cell_index) {
-            if ((rc = st.upload(cell_index, (size_t)N * 8, &d, c->stream))) return rc;
-            cell_index = (const int64_t*)d;
-        }
-    }
+    int rc;
+    if ((rc = st.in(means, (size_t)rows * G, c->stream)) || (rc = st.in(row_of_cell, (size_t)N, c->stream)) ||
+        (rc = st.in(scaling, (size_t)N, c->stream)) || (rc = st.in(alpha, (size_t)G, c->stream)) ||
+        (rc = st.in(beta, (size_t)G, c->stream)) || (rc = st.in(cell_index, (size_t)N, c->stream)))
+        return rc;
     const int64_t n_pad = (N + 15) & ~(int64_t)15;
     const size_t vec_bytes = ((((size_t)n_pad + 3 * (size_t)G) * sizeof(float)) + 255) & ~(size_t)255;
-    int rc = ws_reserve(c, vec_bytes + (geo ? geo->total() : 0));
-    if (rc) return rc;
+    if ((rc = ws_reserve(c, vec_bytes + (geo ? stream_workspace(*geo, N, nullptr).bytes : 0)))) return rc;
     A->means = means;
     A->row_of_cell = row_of_cell;
     A->cell_index = cell_index;
@@ -771,29 +816,15 @@ static int sampler_setup(prosstt_amd_ctx* c, Staging& st, const float* means, in
     A->ga = A->scal + n_pad;
     A->gbm1 = A->ga + G;
     A->gphi = A->gbm1 + G;
-    A->extra = (char*)c->ws + vec_bytes;
-    k3::CellInfo* info = nullptr;
-    A->heavy = k3::HeavyList{};
-    A->heavy_rec = nullptr;
-    if (geo) {
-        char* at = (char*)A->extra;
-        k3::HeavyList& heavy = A->heavy;
-        heavy.list = (uint2*)at; at += geo->list_bytes;
-        heavy.seg_cnt = (uint32_t*)at;                                // zeroed by the preparation kernel
-        A->heavy_rec = (k3::HeavyList*)(at + 768); at += geo->cnt_bytes;
-        heavy.dense = (uint2*)at; at += geo->dense_bytes;
-        heavy.count = (uint32_t*)at; at += geo->count_bytes;
-        heavy.ent = (k3::HeavyEntry*)at; at += geo->ent_bytes;
-        heavy.wst = (k3::f32x4_t*)at; at += geo->wst_bytes;
-        heavy.wid = (uint32_t*)at; at += geo->wid_bytes;
-        heavy.ovf_regions = (uint32_t*)at; at += geo->ovf_bytes;
-        heavy.redo = (int2*)at; at += geo->redo_bytes;
-        info = (k3::CellInfo*)at;
-        heavy.cap = geo->region_cap;
-        heavy.ent_cap = geo->ent_cap;
-        heavy.overflow = (uint32_t*)(c->scratch + 3);           // zeroed by the preparation kernel
+    if (geo) {   // (else *A keeps the empty list and the NULL records its caller initialised it to)
+        const StreamWorkspace w = stream_workspace(*geo, N, (char*)c->ws + vec_bytes);
+        A->heavy = w.heavy;
+        A->heavy.cap = geo->region_cap;
+        A->heavy.ent_cap = geo->ent_cap;
+        A->heavy.overflow = (uint32_t*)(c->scratch + kListOverflow);   // zeroed by the preparation kernel
+        A->heavy_rec = w.heavy_rec;
+        A->cellinfo = w.info;
     }
-    A->cellinfo = info;
     // a checked call needs the per-row flags of THIS mean tensor: scanned now unless the caller vouches that the tensor
     // the ctx last scanned (same pointer, same shape) has not changed since
     const uint8_t* row_bad = nullptr;
@@ -822,7 +853,7 @@ static int sampler_setup(prosstt_amd_ctx* c, Staging& st, const float* means, in
     const int64_t span = (N + 4 > G ? N + 4 : G);
     prep_kernel<<<dim3((unsigned)((span + 255) / 256)), dim3(256), 0, c->stream>>>(
         scaling, N, alpha, beta, G, A->scal, A->ga, A->gbm1, A->gphi, row_of_cell, rows, cell_offset, cell_index,
-        geo ? (int32_t)geo->strip_cells : 1, (uint32_t)seed, (uint32_t)(seed >> 32), info, geo ? c->scratch : nullptr,
+        (uint32_t)seed, (uint32_t)(seed >> 32), A->cellinfo, geo ? c->scratch : nullptr,
         row_bad, c->call_parity, A->heavy, A->heavy_rec);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -880,7 +911,7 @@ PA_EXPORT int prosstt_amd_sample_counts(prosstt_amd_ctx* c, const float* means, 
                                         uint64_t seed, uint64_t cell_offset, const int64_t* cell_index,
                                         int32_t* out, int64_t ld_out, uint32_t flags) try
 {
-    Staging st;
+    Staging st(flags);
     SamplerArgs A{};
     // everything that can be refused is refused before the workspace grows
     if (N > 0 && G > 0) {
@@ -891,7 +922,7 @@ PA_EXPORT int prosstt_amd_sample_counts(prosstt_amd_ctx* c, const float* means, 
         if (N > 0x7fffffffll) return fail(PROSSTT_AMD_EINVAL, "too many cells; chunk them");
         if ((uint64_t)(rows > 0 ? rows : 0) * (uint64_t)G >= ((uint64_t)1 << 61)) return fail(PROSSTT_AMD_EINVAL, "mean tensor too large");
     }
-    const StreamGeometry geo = stream_geometry(N, G, rows);
+    const StreamGeometry geo = stream_geometry(N, G);
     if (geo.groups * geo.tiles_g > 0x1fffffffll) return fail(PROSSTT_AMD_EINVAL, "too many tiles; chunk the cells");
     int rc = sampler_setup(c, st, means, rows, G, row_of_cell, scaling, alpha, beta, N, flags, &A, &geo, cell_offset,
                            cell_index, seed);
@@ -901,11 +932,7 @@ PA_EXPORT int prosstt_amd_sample_counts(prosstt_amd_ctx* c, const float* means, 
     k3::CellInfo* cellinfo = A.cellinfo;
     const int64_t* d_cell_index = A.cell_index;
     int32_t* d_out = out;
-    if (flags & PROSSTT_AMD_HOST_OUTPUT) {
-        void* p = nullptr;
-        if ((rc = st.alloc(&p, (size_t)N * ld_out * 4))) return rc;
-        d_out = (int32_t*)p;
-    }
+    if ((rc = st.out(d_out, (size_t)N * ld_out))) return rc;
 
     const bool vec = (G % 4 == 0) && (ld_out % 4 == 0) && (((uintptr_t)A.means & 15) == 0) &&
                      (((uintptr_t)d_out & 15) == 0);
@@ -950,14 +977,14 @@ PA_EXPORT int prosstt_amd_sample_counts(prosstt_amd_ctx* c, const float* means, 
     c->list_groups = geo.groups;
     c->list_strip_cells = geo.strip_cells;
     c->call_parity ^= 1u;
-    if (flags & PROSSTT_AMD_HOST_OUTPUT)   // G columns of every row; the caller's padding beyond G is left alone
+    if (st.host_out)   // G columns of every row; the caller's padding beyond G is left alone
         HIP_TRY(hipMemcpy2DAsync(out, (size_t)ld_out * 4, d_out, (size_t)ld_out * 4, (size_t)G * 4, (size_t)N,
                                  hipMemcpyDeviceToHost, c->stream));
     if (flags & PROSSTT_AMD_CHECK_DOMAIN) {
         int verdict = 0;
         rc = domain_verdict(c, rows, &verdict);
         if (rc) return rc;
-    } else if (flags & (PROSSTT_AMD_HOST_OUTPUT | PROSSTT_AMD_HOST_INPUTS)) {
+    } else if (st.host_in || st.host_out) {
         HIP_TRY(hipStreamSynchronize(c->stream));   // staging buffers die with `st`
     }
     return 0;
@@ -979,9 +1006,9 @@ PA_EXPORT int prosstt_amd_last_list(prosstt_amd_ctx* c, int64_t* cells, int32_t*
     if (!c->list.seg_cnt) return 0;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    int64_t flagw[4];
-    HIP_TRY(hipMemcpy(flagw, c->scratch, sizeof(flagw), hipMemcpyDeviceToHost));
-    if (overflowed) *overflowed = (int32_t)((uint32_t)flagw[3] != 0u);
+    int64_t overflow = 0;
+    HIP_TRY(hipMemcpy(&overflow, c->scratch + kListOverflow, 8, hipMemcpyDeviceToHost));
+    if (overflowed) *overflowed = (int32_t)((uint32_t)overflow != 0u);
     int64_t written = 0;
     // per region: the first entries and the walks
     std::vector<uint32_t> counts(c->list_regions);
@@ -1027,26 +1054,22 @@ PA_EXPORT int prosstt_amd_nb_params(prosstt_amd_ctx* c, const float* means, int6
                                     const double* alpha, const double* beta, int64_t N, float* mu,
                                     float* p, float* r, int32_t* path, uint32_t flags) try
 {
-    Staging st;
+    Staging st(flags);
     SamplerArgs A{};
     int rc = sampler_setup(c, st, means, rows, G, row_of_cell, scaling, alpha, beta, N, flags, &A, nullptr, 0, nullptr, 0);
     if (rc) return rc;
     if (N == 0 || G == 0) return 0;
-    const size_t bytes = (size_t)N * G * 4;
-    void* d[4] = {mu, p, r, path};
-    void* h[4] = {mu, p, r, path};
-    if (flags & PROSSTT_AMD_HOST_OUTPUT)
-        for (int i = 0; i < 4; ++i)
-            if (h[i] && (rc = st.alloc(&d[i], bytes))) return rc;
     const int64_t total = N * (int64_t)G;
+    float *d_mu = mu, *d_p = p, *d_r = r;
+    int32_t* d_path = path;
+    if ((rc = st.out(d_mu, total)) || (rc = st.out(d_p, total)) || (rc = st.out(d_r, total)) || (rc = st.out(d_path, total))) return rc;
     nb_params_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream>>>(
-        A.means, G, A.row_of_cell, A.scal, A.ga, A.gbm1, N, rows, (float*)d[0], (float*)d[1], (float*)d[2],
-        (int32_t*)d[3]);
+        A.means, G, A.row_of_cell, A.scal, A.ga, A.gbm1, N, rows, d_mu, d_p, d_r, d_path);
     HIP_TRY(hipGetLastError());
-    if (flags & PROSSTT_AMD_HOST_OUTPUT)
-        for (int i = 0; i < 4; ++i)
-            if (h[i]) HIP_TRY(hipMemcpyAsync(h[i], d[i], bytes, hipMemcpyDeviceToHost, c->stream));
-    if (flags & (PROSSTT_AMD_HOST_OUTPUT | PROSSTT_AMD_HOST_INPUTS)) HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((rc = st.back(mu, d_mu, total, c->stream)) || (rc = st.back(p, d_p, total, c->stream)) ||
+        (rc = st.back(r, d_r, total, c->stream)) || (rc = st.back(path, d_path, total, c->stream)))
+        return rc;
+    if (st.host_in || st.host_out) HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 PA_CATCH
@@ -1059,21 +1082,15 @@ PA_EXPORT int prosstt_amd_hw_math(prosstt_amd_ctx* c, int32_t op, uint32_t first
     if ((uint64_t)first_bits + count > ((uint64_t)1 << 32)) return fail(PROSSTT_AMD_EINVAL, "the range leaves the 32-bit patterns");
     if (count == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
+    Staging st(flags);
     float* d = out;
-    Staging st;
-    if (flags & PROSSTT_AMD_HOST_OUTPUT) {
-        void* p = nullptr;
-        int rc = st.alloc(&p, count * 4);
-        if (rc) return rc;
-        d = (float*)p;
-    }
+    int rc;
+    if ((rc = st.out(d, count))) return rc;
     const uint64_t blocks = (count + 255) / 256;
     hw_math_kernel<<<dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, c->stream>>>(op, first_bits, count, d);
     HIP_TRY(hipGetLastError());
-    if (flags & PROSSTT_AMD_HOST_OUTPUT) {
-        HIP_TRY(hipMemcpyAsync(out, d, count * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
+    if ((rc = st.back(out, d, count, c->stream))) return rc;
+    if (st.host_out) HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 PA_CATCH
@@ -1085,25 +1102,16 @@ PA_EXPORT int prosstt_amd_hw_math_at(prosstt_amd_ctx* c, int32_t op, const float
     if (op < 0 || op > 5) return fail(PROSSTT_AMD_EINVAL, "op must be 0 (rcp), 1 (log2), 2 (exp2 of -x), 3 (sqrt), 4 (rsq) or 5 (cos of x revolutions)");
     if (count == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
-    Staging st;
+    Staging st(flags);
     const float* dx = x;
     float* dy = out;
     int rc;
-    if (flags & PROSSTT_AMD_HOST_INPUTS) {
-        const void* p = nullptr;
-        if ((rc = st.upload(x, count * 4, &p, c->stream))) return rc;
-        dx = (const float*)p;
-    }
-    if (flags & PROSSTT_AMD_HOST_OUTPUT) {
-        void* p = nullptr;
-        if ((rc = st.alloc(&p, count * 4))) return rc;
-        dy = (float*)p;
-    }
+    if ((rc = st.in(dx, count, c->stream)) || (rc = st.out(dy, count))) return rc;
     const uint64_t blocks = (count + 255) / 256;
     hw_math_at_kernel<<<dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, c->stream>>>(op, dx, count, dy);
     HIP_TRY(hipGetLastError());
-    if (flags & PROSSTT_AMD_HOST_OUTPUT) HIP_TRY(hipMemcpyAsync(out, dy, count * 4, hipMemcpyDeviceToHost, c->stream));
-    if (flags & (PROSSTT_AMD_HOST_OUTPUT | PROSSTT_AMD_HOST_INPUTS)) HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((rc = st.back(out, dy, count, c->stream))) return rc;
+    if (st.host_in || st.host_out) HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 PA_CATCH
