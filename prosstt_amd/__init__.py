@@ -14,6 +14,11 @@ Principal components of log1p(X / s) on the device (the example notebooks' route
     from prosstt_amd import simulation as sim, embed
     X, pt, br, sc = sim.sample_density(t, n, alpha=a, beta=b, out="torch"); p = embed.pca(X, sc)
 
+Exact k nearest neighbours of the cells on the device (what ``pp.neighbors`` computes, from the PCA scores):
+
+    from prosstt_amd import neighbors
+    nb = neighbors.knn(p.scores, 14)                  # nb.indices, nb.sq_distances, nb.distances, nb.to_csr()
+
 or, for unmodified scripts that say ``from prosstt import ...``:
 
     import prosstt_amd; prosstt_amd.install_as_prosstt()

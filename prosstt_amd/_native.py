@@ -91,10 +91,16 @@ LIBRARIES = {
         "prosstt_amd_embed_matmul": _int(vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, u64, vp),
         "prosstt_amd_embed_rmatmul": _int(vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, u64, vp),
     }, "prosstt_amd_embed_last_error"),
+    # include/prosstt_amd_knn.h: exact k nearest neighbours of the rows of an f32 panel
+    "knn": _Library(_path("PROSSTT_AMD_KNN_LIB", "libprosstt_amd_knn.so"), "prosstt_amd/csrc/knn", True, {
+        "prosstt_amd_knn_last_error": _text,
+        "prosstt_amd_knn_workspace_bytes": _int(i64, i64, i64, i64, _ptr_to(u64)),
+        "prosstt_amd_knn_search": _int(vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, u64),
+    }, "prosstt_amd_knn_last_error"),
 }
 
-LIB_PATH, HOST_LIB_PATH, STATS_LIB_PATH, EMBED_LIB_PATH = (lib.path for lib in LIBRARIES.values())
-SYMBOLS, HOST_SYMBOLS, STATS_SYMBOLS, EMBED_SYMBOLS = (list(lib.symbols) for lib in LIBRARIES.values())
+LIB_PATH, HOST_LIB_PATH, STATS_LIB_PATH, EMBED_LIB_PATH, KNN_LIB_PATH = (lib.path for lib in LIBRARIES.values())
+SYMBOLS, HOST_SYMBOLS, STATS_SYMBOLS, EMBED_SYMBOLS, KNN_SYMBOLS = (list(lib.symbols) for lib in LIBRARIES.values())
 
 
 class NativeError(RuntimeError):
@@ -162,6 +168,11 @@ def load_embed():
     return _load("embed")
 
 
+def load_knn():
+    """libprosstt_amd_knn.so (include/prosstt_amd_knn.h), once.  Raises if it has not been built."""
+    return _load("knn")
+
+
 def check(code):
     _check("sampler", code)
 
@@ -172,6 +183,10 @@ def check_stats(code):
 
 def check_embed(code):
     _check("embed", code)
+
+
+def check_knn(code):
+    _check("knn", code)
 
 
 def device_count():

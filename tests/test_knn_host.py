@@ -1,0 +1,124 @@
+"""neighbors.knn without a device: the scalar model (tests/knn_model.py) against a binary64 brute force and on exact ties;
+the argument checks that refuse before any device use; the header, the loader's table and the built library name the
+same symbols; Neighbors.distances and to_csr() on a hand-made result."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+import knn_model
+
+torch = pytest.importorskip("torch")
+
+from prosstt_amd import _native, neighbors  # noqa: E402
+
+
+def test_model_against_binary64():
+    N, d, k = 1500, 50, 15
+    P = knn_model.gaussian(N, d, 20261018)
+    idx, d2 = knn_model.model(P, k)
+    ref_idx, ref_d2 = knn_model.brute64(P, k)
+    assert idx.dtype == np.int32 and d2.dtype == np.float32 and idx.shape == d2.shape == (N, k)
+    np.testing.assert_array_equal(idx, ref_idx)
+    # d roundings of the sum, one of each square and of each difference (2 per term, relative to the term): below
+    # (d + 2) 2^-24 of the sum of non-negative terms
+    assert np.all(np.abs(d2.astype(np.float64) - ref_d2) <= (d + 2) * 2.0 ** -24 * ref_d2)
+    assert np.all(np.diff(d2, axis=1) >= 0) and not np.any(idx == np.arange(N)[:, None])
+
+
+def test_model_resolves_ties_to_the_lower_index():
+    N, k = 1000, 15
+    P = knn_model.lattice(N, 7)
+    idx, d2 = knn_model.model(P, k)
+    full = ((P[:, None, :].astype(np.float64) - P[None, :, :]) ** 2).sum(axis=2)     # small integers: exact
+    tied = 0
+    for i in range(N):
+        row = full[i].copy()
+        row[i] = np.inf
+        kth = np.sort(row)[k - 1]
+        tied += int(np.sort(row)[k] == kth)
+        below = np.flatnonzero(row < kth)
+        equal = np.flatnonzero(row == kth)[:k - below.size]          # the lowest indices among the tied
+        want = np.concatenate([below, equal])
+        want = want[np.lexsort((want, row[want]))]
+        np.testing.assert_array_equal(idx[i], want)
+        np.testing.assert_array_equal(d2[i], row[want].astype(np.float32))
+    assert tied > N // 2, tied
+
+
+def test_symmetric_bits():
+    P = knn_model.scaled(300, 33, 3)
+    idx, d2 = knn_model.model(P, 299)
+    full = np.empty((300, 300), np.float32)
+    np.put_along_axis(full, idx, d2, axis=1)
+    np.fill_diagonal(full, 0)
+    np.testing.assert_array_equal(full.view(np.uint32), full.T.view(np.uint32))
+    assert knn_model.no_subnormal_terms(P)
+
+
+def test_refusals_before_any_device_use():
+    P = knn_model.gaussian(20, 5, 1)
+    with pytest.raises(TypeError, match="floating"):
+        neighbors.knn(P.astype(np.int32), 3)
+    with pytest.raises(TypeError, match="floating"):
+        neighbors.knn(torch.ones((20, 5), dtype=torch.int64), 3)
+    with pytest.raises(ValueError, match="dimensions"):
+        neighbors.knn(P[0], 3)
+    with pytest.raises(ValueError, match="dimensions"):
+        neighbors.knn(P.reshape(2, 10, 5), 3)
+    with pytest.raises(ValueError, match="cells"):
+        neighbors.knn(P[:1], 1)
+    with pytest.raises(ValueError, match="coordinates"):
+        neighbors.knn(np.zeros((20, 0), np.float32), 3)
+    with pytest.raises(ValueError, match="coordinates"):
+        neighbors.knn(np.zeros((20, 129), np.float32), 3)
+    for k in (0, -1, 20, 2.5):
+        with pytest.raises(ValueError, match="n_neighbors"):
+            neighbors.knn(P, k)
+    with pytest.raises(ValueError, match="n_neighbors"):
+        neighbors.knn(np.zeros((2000, 2), np.float32), 1025)
+    with pytest.raises(ValueError, match="out must be"):
+        neighbors.knn(P, 3, out="csr")
+    for chunk in (0, 21, 1.5):
+        with pytest.raises(ValueError, match="chunk_rows"):
+            neighbors.knn(P, 3, chunk_rows=chunk)
+    for bad in (np.nan, np.inf, -np.inf, 2.0 ** 59, -2.0 ** 60):
+        Q = P.astype(np.float64)
+        Q[7, 2] = bad
+        with pytest.raises(ValueError, match="finite"):
+            neighbors.knn(Q, 3)
+        with pytest.raises(ValueError, match="finite"):
+            neighbors.knn(torch.as_tensor(Q), 3)                  # a CPU tensor is a host array
+
+
+def test_library_exports_every_declared_symbol():
+    header = open(os.path.join(ROOT, "include", "prosstt_amd_knn.h")).read()
+    declared = set(re.findall(r"\b(prosstt_amd_knn_[a-z_0-9]+)\s*\(", header))
+    assert declared == set(_native.KNN_SYMBOLS)
+    assert len(declared) == 3
+    if os.path.exists(_native.KNN_LIB_PATH):
+        lib = ctypes.CDLL(_native.KNN_LIB_PATH)
+        for name in declared:
+            assert hasattr(lib, name), name
+
+
+def test_neighbors_result():
+    pytest.importorskip("scipy")
+    idx = np.array([[2, 1], [0, 3], [3, 0], [2, 1]], dtype=np.int32)
+    d2 = np.array([[0.0, 4.0], [4.0, 9.0], [0.25, 0.25], [0.25, 16.0]], dtype=np.float32)
+    nb = neighbors.Neighbors(idx, d2)
+    assert nb.indices is idx and nb.sq_distances is d2
+    dist = nb.distances
+    assert dist.dtype == np.float64
+    np.testing.assert_array_equal(dist, [[0.0, 2.0], [2.0, 3.0], [0.5, 0.5], [0.5, 4.0]])
+    g = nb.to_csr()
+    assert g.shape == (4, 4) and g.dtype == np.float64 and g.nnz == 8
+    np.testing.assert_array_equal(g.indptr, [0, 2, 4, 6, 8])
+    np.testing.assert_array_equal(g.indices, [1, 2, 0, 3, 0, 3, 1, 2])
+    np.testing.assert_array_equal(g.data, [2.0, 0.0, 2.0, 3.0, 0.5, 0.5, 4.0, 0.5])
+    t = neighbors.Neighbors(torch.as_tensor(idx), torch.as_tensor(d2))               # tensors: the same graph
+    assert t.distances.dtype == torch.float64
+    assert (t.to_csr() != g).nnz == 0
