@@ -13,7 +13,7 @@ import numpy as np
 from numpy import random
 
 from . import device as _device
-from .device import HOST_OUTS as _HOST_OUTS, OUT_CHOICES as _OUT_CHOICES, host_return as _host_return
+from . import simulation as _sim          # (imports this module in turn: only used inside functions)
 
 
 def generate_negbin_params(tree, mean_alpha=0.2, mean_beta=2, a_scale=1.5, b_scale=1.5):
@@ -45,10 +45,10 @@ def sample_counts(mu, alpha, beta, *, seed=None, out="numpy", strict=True):
     mu = np.ascontiguousarray(mu, dtype=np.float32)
     if mu.ndim != 2:
         raise ValueError("mu must be (cells, genes)")
+    _sim._check_out(out)
     N, G = mu.shape
     if seed is None:
-        lo, hi = random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
-        seed = int(lo) | (int(hi) << 32)
+        seed = _sim._default_seed()
     ctx = _device.get_context()
     counts = ctx.sample_counts(mu, np.arange(N, dtype=np.int32), np.ones(N),
                                np.broadcast_to(np.asarray(alpha, dtype=np.float64), (G,)),
@@ -56,6 +56,4 @@ def sample_counts(mu, alpha, beta, *, seed=None, out="numpy", strict=True):
                                seed=seed, check_domain=strict)
     if out == "torch":
         return counts
-    if out not in _HOST_OUTS:
-        raise ValueError(_OUT_CHOICES)
-    return _host_return(counts, out)
+    return _device.host_return(counts, out)

@@ -342,6 +342,14 @@ def plan_order(row_of_cell, rows=None):
     return order
 
 
+def inverse_permutation(perm):
+    """int64 array ``inv`` with ``inv[perm[i]] = i``: the row of every cell, from the cell of every row."""
+    perm = np.asarray(perm, dtype=np.int64)
+    inv = np.empty(perm.size, dtype=np.int64)
+    inv[perm] = np.arange(perm.size, dtype=np.int64)
+    return inv
+
+
 def host_fingerprint(arrays):
     """Identity and content fingerprint of host arrays that a device tensor mirrors: the caches of
     ``Tree.device_means`` and of ``simulate_lineage`` compare it before they trust their device copy,
@@ -707,9 +715,7 @@ def _device_rows(row_order, n, dev):
     order = np.asarray(row_order, dtype=np.int64)
     if order.shape != (n,):
         raise ValueError("row_order must have one entry per row")
-    inv = np.empty(n, dtype=np.int64)
-    inv[order] = np.arange(n, dtype=np.int64)
-    return _torch().as_tensor(inv).to(dev)
+    return _torch().as_tensor(inverse_permutation(order)).to(dev)
 
 
 _free_blocks = []              # pageable result memory that no result holds, oldest first; see _result_array
@@ -847,9 +853,7 @@ class PresentedCounts:
     @property
     def row_of_cell(self):
         if self._row_of_cell is None:
-            inv = np.empty_like(self.cell_of_row)
-            inv[self.cell_of_row] = np.arange(self.cell_of_row.size, dtype=np.int64)
-            self._row_of_cell = inv
+            self._row_of_cell = inverse_permutation(self.cell_of_row)
         return self._row_of_cell
 
     def in_plan_order(self):

@@ -106,11 +106,9 @@ class LogNormalized:
         self.counts, self.ld, self.device, self.dtype = X, m.ld, X.device, torch.float32
         self._row_of_cell = self._cell_of_row = None
         if cell_of_row is not None:
-            row_of_cell = np.empty_like(cell_of_row)
-            row_of_cell[cell_of_row] = np.arange(N, dtype=np.int64)
             inv = inv[cell_of_row]                                    # row i of X is cell cell_of_row[i]
             self._cell_of_row = torch.as_tensor(cell_of_row).to(X.device)
-            self._row_of_cell = torch.as_tensor(row_of_cell).to(X.device)
+            self._row_of_cell = torch.as_tensor(_device.inverse_permutation(cell_of_row)).to(X.device)
         self.inv_size = torch.as_tensor(inv).to(X.device)
         self.status = torch.zeros(1, dtype=torch.int32, device=X.device)
 

@@ -41,6 +41,11 @@ def world(group=None):
     return 0, 1
 
 
+def _peer(group, r):
+    """Rank ``r`` of ``group`` as P2POp addresses it: by its GLOBAL rank."""
+    return _dist().get_global_rank(group, r) if group is not None else r
+
+
 def assign_branches_to_ranks(branch_of_cell, world_size):
     """owner[label] -> rank.  Longest-processing-time greedy on cells per branch: branches
     in decreasing cell count (ties by first appearance) go to the least-loaded rank."""
@@ -173,6 +178,14 @@ def cells_of_rank(branch_of_cell, owner, rank):
     return np.nonzero(mine)[0].astype(np.int64)
 
 
+def _rank_cells(tree, branch_of_cell, rank, size):
+    """Positions in the plan (ascending) of the cells that ``rank`` of ``size`` samples."""
+    if tree._branch_owner is not None and size > 1:
+        # the tree was built sharded: a cell is sampled where its branch's rows are
+        return cells_of_rank(branch_of_cell, tree._branch_owner, rank)
+    return shard_cells(branch_of_cell, rank, size)[0]
+
+
 def broadcast_plan(plan, group=None, src=0):
     """Make every rank use rank ``src``'s ``(pseudotime, branches, scalings, seed)``.
 
@@ -266,35 +279,34 @@ def sample_density_sharded(tree, no_cells, alpha=0.3, beta=2, scale=True, scale_
     draws of the single-process call), then rank 0's values are broadcast: ranks that were seeded
     alike stay in lock-step for whatever they draw next, and ranks that were not still sample one
     plan.  With ``strict`` the ranks also compare a digest of their mean tensor, alpha and beta."""
+    sim._check_order(order)
     rank, size = world(group)
+    pt, br, sc, seed, alpha, beta = _sharded_plan(tree, no_cells, alpha, beta, scale, scale_v, scale_mean, seed, group, strict)
+    mine = _rank_cells(tree, br, rank, size)
+    ctx = _device.get_context()
+    rows = sim.cell_rows(tree, pt[mine], br[mine])
+    # row i of `counts` is the cell at position `mine[i]` of the plan, which is what every consumer of the pair goes by
+    counts, perm = sim._launch_cells(ctx, tree.device_means(), None, rows, sc[mine], alpha, beta, seed, mine,
+                                     order == "presented", strict)
+    if perm is not None:
+        mine = mine[perm]
+    return counts, mine, pt, br, sc
+
+
+def _sharded_plan(tree, no_cells, alpha, beta, scale, scale_v, scale_mean, seed, group, strict):
+    """``(pseudotime, branches, scalings, seed, alpha, beta)`` of a sharded call, the same on every rank of ``group``:
+    EVERY rank draws the plan, the scalings and the default seed from its own numpy stream (the draws of the
+    single-process call), then rank 0's values are broadcast.  alpha and beta come back one per gene; on a replicated tree
+    ``strict`` compares them and the mean tensor across the ranks (a tree built sharded was agreed on when it was built)."""
     pt, br = sim._density_plan(tree, no_cells)
     sc = sut.calc_scalings(no_cells, scale, scale_mean, scale_v)
     if seed is None:
-        lo, hi = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
-        seed = int(lo) | (int(hi) << 32)
+        seed = sim._default_seed()
     pt, br, sc, seed = broadcast_plan((pt, br, sc, seed), group)
-    alpha = np.full(tree.G, alpha, np.float64) if np.ndim(alpha) == 0 else np.asarray(alpha, np.float64)
-    beta = np.full(tree.G, beta, np.float64) if np.ndim(beta) == 0 else np.asarray(beta, np.float64)
-    if tree._branch_owner is not None and size > 1:
-        # the tree was built sharded: a cell is sampled where its branch's rows are
-        mine = cells_of_rank(br, tree._branch_owner, rank)
-    else:
-        mine, _ = shard_cells(br, rank, size)
-        if strict:
-            assert_replicas_agree(tree, alpha, beta, group)
-    ctx = _device.get_context()
-    rows = sim.cell_rows(tree, pt[mine], br[mine])
-    # the rank's cells are presented grouped by their row of the mean tensor (simulation.draw_counts says why); row i of
-    # `counts` is the cell at position `mine[i]` of the plan, which is what every consumer of the pair goes by
-    if order not in ("presented", "plan"):
-        raise ValueError("order must be 'presented' or 'plan'")
-    means = tree.device_means()
-    mine = np.asarray(mine, dtype=np.int64)
-    if order == "presented":
-        perm = _device.plan_order(rows, means.shape[0])
-        mine, rows = mine[perm], rows[perm]
-    counts = ctx.sample_counts(means, rows, sc[mine], alpha, beta, seed=seed, cell_index=mine, check_domain=strict)
-    return counts, mine, pt, br, sc
+    alpha, beta = sim._per_gene(alpha, tree.G), sim._per_gene(beta, tree.G)
+    if strict and tree._branch_owner is None:
+        assert_replicas_agree(tree, alpha, beta, group)                # (returns at once in a single process)
+    return pt, br, sc, seed, alpha, beta
 
 
 def presentation_key(tree, pseudotime, branches):
@@ -319,10 +331,7 @@ def shards_in_presentation_order(tree, pseudotime, branches, size):
     key = presentation_key(tree, pseudotime, branches)
     shards = []
     for r in range(size):
-        if tree._branch_owner is not None and size > 1:
-            cells = cells_of_rank(branches, tree._branch_owner, r)
-        else:
-            cells = shard_cells(branches, r, size)[0]
+        cells = _rank_cells(tree, branches, r, size)
         shards.append(cells[np.argsort(key[cells], kind="stable")])
     return shards
 
@@ -350,16 +359,7 @@ def sample_and_gather(tree, no_cells, alpha=0.3, beta=2, scale=True, scale_v=0.7
     if order not in ("shard", "plan"):
         raise ValueError("order must be 'shard' or 'plan'")
     rank, size = world(group)
-    pt, br = sim._density_plan(tree, no_cells)
-    sc = sut.calc_scalings(no_cells, scale, scale_mean, scale_v)
-    if seed is None:
-        lo32, hi32 = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
-        seed = int(lo32) | (int(hi32) << 32)
-    pt, br, sc, seed = broadcast_plan((pt, br, sc, seed), group)
-    alpha = np.full(tree.G, alpha, np.float64) if np.ndim(alpha) == 0 else np.asarray(alpha, np.float64)
-    beta = np.full(tree.G, beta, np.float64) if np.ndim(beta) == 0 else np.asarray(beta, np.float64)
-    if strict and size > 1 and tree._branch_owner is None:
-        assert_replicas_agree(tree, alpha, beta, group)
+    pt, br, sc, seed, alpha, beta = _sharded_plan(tree, no_cells, alpha, beta, scale, scale_v, scale_mean, seed, group, strict)
     shards = shards_in_presentation_order(tree, pt, br, size)
     mine = shards[rank]
     sizes = [len(c) for c in shards]
@@ -373,9 +373,7 @@ def sample_and_gather(tree, no_cells, alpha=0.3, beta=2, scale=True, scale_v=0.7
     chunk = int(chunk_cells) if chunk_cells else max(1, int(chunk_bytes) // (4 * G))
     rounds = (max(sizes) + chunk - 1) // chunk if max(sizes) else 0
     is_root = rank == dst
-
-    def peer(r):                     # P2POp addresses GLOBAL ranks
-        return dist.get_global_rank(group, r) if group is not None else r
+    verdict = sim._DeferredVerdict(ctx, strict)
 
     if is_root:
         out = torch.empty((no_cells, G), dtype=torch.int32, device=dev)
@@ -390,7 +388,8 @@ def sample_and_gather(tree, no_cells, alpha=0.3, beta=2, scale=True, scale_v=0.7
         lo, hi = r * chunk, min((r + 1) * chunk, sizes[rank])
         if lo < hi:
             ctx.sample_counts(means, rows[lo:hi], sc[mine[lo:hi]], alpha, beta, seed=seed, cell_index=mine[lo:hi],
-                              out=local[lo:hi], check_domain="deferred" if strict else False, means_token=token)
+                              out=local[lo:hi], check_domain=verdict.mode, means_token=token)
+            verdict.enqueued()
         return lo, hi
 
     def post_receives(r):
@@ -403,7 +402,7 @@ def sample_and_gather(tree, no_cells, alpha=0.3, beta=2, scale=True, scale_v=0.7
             buf = out[first_row[src] + lo:first_row[src] + hi] if order == "shard" else \
                 torch.empty((hi - lo, G), dtype=torch.int32, device=dev)
             got.append((src, lo, hi, buf))
-            ops.append(dist.P2POp(dist.irecv, buf, peer(src), group))
+            ops.append(dist.P2POp(dist.irecv, buf, _peer(group, src), group))
         return got, (dist.batch_isend_irecv(ops) if ops else [])
 
     def land(got):
@@ -417,32 +416,31 @@ def sample_and_gather(tree, no_cells, alpha=0.3, beta=2, scale=True, scale_v=0.7
     # round r's receives only after round r - 1 has arrived, and an unbounded queue of sends has nowhere to go on a
     # backend with a fixed number of point-to-point channels.
     sends, pending = [], ([], [])
-    for r in range(rounds):
-        lo, hi = sample(r)                                   # enqueued; the transfers below are ordered behind it
-        if size > 1 and not is_root and lo < hi:
-            if len(sends) >= 2:
-                for req in sends[-2]:
+    with verdict:                                            # (whatever fails below: no verdict outlives the call)
+        for r in range(rounds):
+            lo, hi = sample(r)                                   # enqueued; the transfers below are ordered behind it
+            if size > 1 and not is_root and lo < hi:
+                if len(sends) >= 2:
+                    for req in sends[-2]:
+                        req.wait()
+                _host_backend_fence(group)                         # (gloo only: the chunk has been sampled)
+                sends.append(dist.batch_isend_irecv([dist.P2POp(dist.isend, local[lo:hi], _peer(group, dst), group)]))
+            if size > 1 and is_root:
+                got, reqs = pending
+                for req in reqs:
                     req.wait()
-            _host_backend_fence(group)                         # (gloo only: the chunk has been sampled)
-            sends.append(dist.batch_isend_irecv([dist.P2POp(dist.isend, local[lo:hi], peer(dst), group)]))
-        if size > 1 and is_root:
+                pending = post_receives(r)                       # round r travels while round r + 1 is sampled
+                land(got)                                        # (order="plan": round r - 1 is scattered under it)
+        for reqs_ in sends[-2:]:
+            for req in reqs_:
+                req.wait()
+        if is_root:
             got, reqs = pending
             for req in reqs:
                 req.wait()
-            pending = post_receives(r)                       # round r travels while round r + 1 is sampled
-            land(got)                                        # (order="plan": round r - 1 is scattered under it)
-    for reqs_ in sends[-2:]:
-        for req in reqs_:
-            req.wait()
-    if is_root:
-        got, reqs = pending
-        for req in reqs:
-            req.wait()
-        land(got)
-        if order == "plan":
-            out.index_copy_(0, torch.as_tensor(mine, dtype=torch.int64, device=dev), local)
-    if strict:
-        ctx.domain_status()
+            land(got)
+            if order == "plan":
+                out.index_copy_(0, torch.as_tensor(mine, dtype=torch.int64, device=dev), local)
     cell_of_row = np.concatenate(shards) if order == "shard" else None
     return out, cell_of_row, pt, br, sc
 
@@ -494,9 +492,6 @@ def gather_rows(local_rows, cell_index, total_rows, group=None, dst=0, chunk_row
     if chunk_rows is None:
         chunk_rows = max(1, int(chunk_bytes) // max(1, G * local_rows.element_size()))
 
-    def peer(r):                     # P2POp addresses GLOBAL ranks
-        return dist.get_global_rank(group, r) if group is not None else r
-
     comm_dev = local_rows.device
     if index_of_rank is not None:
         if len(index_of_rank) != size or len(index_of_rank[rank]) != local_rows.shape[0]:
@@ -515,13 +510,13 @@ def gather_rows(local_rows, cell_index, total_rows, group=None, dst=0, chunk_row
             for src in range(size):
                 if src != dst and sizes[src]:
                     where[src] = torch.empty(sizes[src], dtype=torch.int64, device=comm_dev)
-                    ops.append(dist.P2POp(dist.irecv, where[src], peer(src), group))
+                    ops.append(dist.P2POp(dist.irecv, where[src], _peer(group, src), group))
             for req in (dist.batch_isend_irecv(ops) if ops else []):
                 req.wait()
         elif sizes[rank]:
             index = index.contiguous()
             _host_backend_fence(group)
-            for req in dist.batch_isend_irecv([dist.P2POp(dist.isend, index, peer(dst), group)]):
+            for req in dist.batch_isend_irecv([dist.P2POp(dist.isend, index, _peer(group, dst), group)]):
                 req.wait()
     rounds = max((n + chunk_rows - 1) // chunk_rows for n in sizes) if max(sizes) else 0
     if rank != dst:
@@ -531,7 +526,7 @@ def gather_rows(local_rows, cell_index, total_rows, group=None, dst=0, chunk_row
             lo, hi = r * chunk_rows, min((r + 1) * chunk_rows, sizes[rank])
             if lo >= hi:
                 break
-            for req in dist.batch_isend_irecv([dist.P2POp(dist.isend, rows[lo:hi], peer(dst), group)]):
+            for req in dist.batch_isend_irecv([dist.P2POp(dist.isend, rows[lo:hi], _peer(group, dst), group)]):
                 req.wait()
         return None
     if to_host:
@@ -550,7 +545,7 @@ def gather_rows(local_rows, cell_index, total_rows, group=None, dst=0, chunk_row
                 continue
             buf = torch.empty((n, G), dtype=local_rows.dtype, device=local_rows.device)
             bufs.append((where[src][r * chunk_rows:r * chunk_rows + n], buf))
-            ops.append(dist.P2POp(dist.irecv, buf, peer(src), group))
+            ops.append(dist.P2POp(dist.irecv, buf, _peer(group, src), group))
         return bufs, (dist.batch_isend_irecv(ops) if ops else [])
 
     pending = post(0) if rounds else ([], [])

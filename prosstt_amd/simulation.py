@@ -22,7 +22,7 @@ import pandas as pd
 from . import count_model as cm
 from . import device as _device
 from . import sim_utils as sut
-from .device import HOST_OUTS as _HOST_OUTS, OUT_CHOICES as _OUT_CHOICES, host_return as _host_return
+from .device import host_return as _host_return
 
 
 # ----------------------------------------------------------------------------------
@@ -267,8 +267,7 @@ def _lineage_loop(tree, ctx, evaluate, commit, rel_exp_cutoff, intra_branch_tol,
     if rng not in ("numpy", "device"):
         raise ValueError("rng must be 'numpy' or 'device'")
     if rng == "device" and seed is None:
-        lo, hi = random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
-        seed = int(lo) | (int(hi) << 32)
+        seed = _default_seed()
     if rng == "device" and tree.modules < 2:
         raise ValueError("at least 2 expression programs are needed")
     topology = np.array(tree.topology)
@@ -383,6 +382,28 @@ def _plain_label(tree, label):
 # sampling (host plan + device K3)
 # ----------------------------------------------------------------------------------
 
+def _default_seed():
+    """The 64-bit seed of a call that was given none: two 32-bit draws from numpy's global stream, so that
+    ``np.random.seed`` still determines the whole simulation."""
+    lo, hi = random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
+    return int(lo) | (int(hi) << 32)
+
+
+def _per_gene(value, genes):
+    """alpha or beta as the sampler takes it: a float64 array with one entry per gene; a scalar applies to every gene."""
+    return np.full(genes, value, dtype=np.float64) if np.ndim(value) == 0 else np.asarray(value, dtype=np.float64)
+
+
+def _check_out(out):
+    if out != "torch" and out not in _device.HOST_OUTS:
+        raise ValueError(_device.OUT_CHOICES)
+
+
+def _check_order(order):
+    if order not in ("presented", "plan"):
+        raise ValueError("order must be 'presented' or 'plan'")
+
+
 def sample_whole_tree_restricted(tree, alpha=0.2, beta=3, **device_opts):
     """Default one-shot simulation (simulation.py:289-316); returns 4 values like the
     reference does (its docstring lists 3)."""
@@ -447,58 +468,15 @@ def sample_density_chunks(tree, no_cells, chunk_cells, alpha=0.3, beta=2, scale=
     ``device.PresentedCounts`` -- the chunk's device tensor in the order its cells were presented, and the permutation --
     or, with ``order="plan"``, plain device tensors in plan order; the consumer must be done with a chunk before asking
     for the next chunk but one)."""
-    if out != "torch" and out not in _HOST_OUTS:
-        raise ValueError(_OUT_CHOICES)
-    if order not in ("presented", "plan"):
-        raise ValueError("order must be 'presented' or 'plan'")
+    _check_out(out)
+    _check_order(order)
     if chunk_cells <= 0:
         raise ValueError("chunk_cells must be positive")
-    alpha, beta = (np.full(tree.G, v, dtype=np.float64) if np.ndim(v) == 0 else np.asarray(v, dtype=np.float64)
-                   for v in (alpha, beta))
+    alpha, beta = _per_gene(alpha, tree.G), _per_gene(beta, tree.G)
     sample_time, sample_branches = _density_plan(tree, no_cells)
     scalings = sut.calc_scalings(no_cells, scale, scale_mean, scale_v)
-    if seed is None:
-        lo, hi = random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
-        seed = int(lo) | (int(hi) << 32)
-    ctx = _device.get_context()
-    rows = cell_rows(tree, sample_time, sample_branches)
-    token = tree.means_token()
-    means = tree.device_means()
-
-    def launch(lo):
-        # (presented grouped by mean-tensor row, put back in plan order inside the copy to the host: see draw_counts)
-        hi = min(lo + chunk_cells, no_cells)
-        if out == "torch" and order == "plan":
-            return ctx.sample_counts(means, rows[lo:hi], scalings[lo:hi], alpha, beta, seed=seed, cell_offset=lo,
-                                     check_domain="deferred" if strict else False, means_token=token), None
-        perm = _device.plan_order(rows[lo:hi], means.shape[0])
-        return ctx.sample_counts(means, rows[lo:hi][perm], scalings[lo:hi][perm], alpha, beta, seed=seed,
-                                 cell_index=lo + perm.astype(np.int64),
-                                 check_domain="deferred" if strict else False, means_token=token), perm
-
-    # The verdict of the deferred domain check is sticky in the ctx and covers every chunk enqueued so far (an invalid
-    # chunk i + 1 may already be reported with chunk i: the plan is one call).  Whatever ends the generator -- exhaustion,
-    # an exception of the host copy, the consumer dropping it -- leaves no verdict behind for an unrelated later call.
-    # (verdict_open: a checked launch has been enqueued whose verdict nobody has read yet)
-    verdict_open = False
-    pending = launch(0) if no_cells else None
-    verdict_open = strict and pending is not None
-    try:
-        for lo in range(0, no_cells, chunk_cells):
-            hi = min(lo + chunk_cells, no_cells)
-            counts, perm = pending
-            pending = launch(hi) if hi < no_cells else None      # enqueued behind `counts`, runs under its copy
-            if out == "torch":
-                host = counts if perm is None else _device.PresentedCounts(counts, perm)
-            else:
-                host = _host_return(counts, out, row_order=perm)
-            if strict:
-                ctx.domain_status()
-                verdict_open = pending is not None               # (the next chunk's launch is already behind it)
-            yield host, sample_time[lo:hi], sample_branches[lo:hi], scalings[lo:hi]
-    finally:
-        if verdict_open:
-            _discard_verdict(ctx)
+    ranges = [(lo, min(lo + chunk_cells, no_cells)) for lo in range(0, no_cells, chunk_cells)]
+    yield from _sample_ranges(tree, sample_time, sample_branches, scalings, alpha, beta, ranges, seed, out, strict, order)
 
 
 def sample_whole_tree(tree, n_factor, alpha=0.3, beta=2, scale=True, scale_mean=0., scale_v=0.7,
@@ -526,7 +504,7 @@ def _sample_data_at_times(tree, sample_pt, branches=None, alpha=0.3, beta=2, sca
                           scale_mean=0., scale_v=0.7, **device_opts):
     """Counts for cells at given pseudotimes (simulation.py:551-599)."""
     # scalar hyper-parameters apply to every gene; branches are drawn before the scalings (stream order)
-    alpha, beta = (np.full(tree.G, v) if np.ndim(v) == 0 else v for v in (alpha, beta))
+    alpha, beta = _per_gene(alpha, tree.G), _per_gene(beta, tree.G)
     if branches is None:
         branches = sut.pick_branches(tree, sample_pt)
     scalings = sut.calc_scalings(len(sample_pt), scale, scale_mean, scale_v)
@@ -592,48 +570,103 @@ def draw_counts(tree, pseudotime, branches, scalings, alpha, beta, *, seed=None,
     no_cells = len(branches)
     if len(pseudotime) != no_cells or len(scalings) != no_cells:
         raise ValueError("pseudotime, branches and scalings must have one entry per cell")
+    _check_out(out)
+    _check_order(order)
+    alpha, beta = np.asarray(alpha, dtype=np.float64), np.asarray(beta, dtype=np.float64)
+    (whole,) = _sample_ranges(tree, pseudotime, branches, np.asarray(scalings, dtype=np.float64), alpha, beta,
+                              [(0, no_cells)], seed, out, strict, order)
+    return whole[0]
+
+
+def _sample_ranges(tree, pseudotime, branches, scalings, alpha, beta, ranges, seed, out, strict, order):
+    """The core of ``draw_counts`` (the one range of all cells) and of ``sample_density_chunks``: a generator of ``(counts,
+    pseudotime, branches, scalings)`` for the successive ``ranges`` (lo, hi) of the cells of ONE plan, ``counts`` in the form
+    that ``out`` and ``order`` name.  The next range is enqueued on the device before a range is copied and handed over."""
     if seed is None:
-        lo, hi = random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
-        seed = int(lo) | (int(hi) << 32)
+        seed = _default_seed()
     ctx = _device.get_context()
     rows = cell_rows(tree, pseudotime, branches)
-    if out != "torch" and out not in _HOST_OUTS:
-        raise ValueError(_OUT_CHOICES)
-    # the domain check rides in the call's own kernels and is not waited for; its verdict is read behind the copy to the
-    # host (which synchronises anyway), or at once when the device tensor itself is returned
-    if order not in ("presented", "plan"):
-        raise ValueError("order must be 'presented' or 'plan'")
     token = tree.means_token()
     means = tree.device_means()
-    scalings = np.asarray(scalings, dtype=np.float64)
-    if out == "torch" and order == "plan":
-        counts = ctx.sample_counts(means, rows, scalings, np.asarray(alpha, dtype=np.float64), np.asarray(beta, dtype=np.float64),
-                                   seed=seed, check_domain="deferred" if strict else False, means_token=token)
-        if strict:
-            ctx.domain_status()
-        return counts
-    # The cells are PRESENTED to the sampler grouped by their row of the mean tensor (every count is keyed by the cell's
-    # position in the plan -- cell_index --, so the matrix is the same whatever the order): the kernel then finds a gene
-    # tile's rows of the mean tensor in cache instead of fetching them once per cell, 2 to 5 % of its time
-    # (profiles/r05_ablation.txt).  The device matrix is in the order of presentation; the copy to the host puts the rows
-    # back in plan order chunk by chunk (a gather on the device, under the transfer of the previous chunk).
-    perm = _device.plan_order(rows, means.shape[0])
-    counts = ctx.sample_counts(means, rows[perm], scalings[perm], np.asarray(alpha, dtype=np.float64),
-                               np.asarray(beta, dtype=np.float64), seed=seed, cell_index=perm.astype(np.int64),
-                               check_domain="deferred" if strict else False, means_token=token)
-    if out == "torch":
-        if strict:
-            ctx.domain_status()
-        return _device.PresentedCounts(counts, perm)
-    try:
-        host = _host_return(counts, out, row_order=perm)
-    except BaseException:
-        if strict:
-            _discard_verdict(ctx)       # (an OverflowError of "numpy16", a failed page-lock: the call's verdict must not outlive it)
-        raise
-    if strict:
-        ctx.domain_status()
-    return host
+    verdict = _DeferredVerdict(ctx, strict)
+    # (the device tensor itself is handed over in plan order only where the caller asks for that; a host array is put back
+    # in plan order inside its copy)
+    presented = not (out == "torch" and order == "plan")
+
+    def launch(lo, hi):
+        sampled = _launch_cells(ctx, means, token, rows[lo:hi], scalings[lo:hi], alpha, beta, seed, lo, presented, verdict.mode)
+        verdict.enqueued()
+        return sampled
+
+    with verdict:
+        pending = launch(*ranges[0]) if ranges else None
+        for i, (lo, hi) in enumerate(ranges):
+            counts, perm = pending
+            pending = launch(*ranges[i + 1]) if i + 1 < len(ranges) else None    # enqueued behind `counts`, runs under its copy
+            if out == "torch":
+                counts = counts if perm is None else _device.PresentedCounts(counts, perm)
+            else:
+                counts = _host_return(counts, out, row_order=perm)
+            # read behind the copy to the host, which synchronises anyway, or at once when the device tensor itself is returned
+            verdict.read(still_open=pending is not None)                        # (the next range's launch is already behind it)
+            yield counts, pseudotime[lo:hi], branches[lo:hi], scalings[lo:hi]
+
+
+def _launch_cells(ctx, means, token, rows, scalings, alpha, beta, seed, at, presented, check):
+    """One launch of the sampler for cells of one plan: ``(counts, perm)``.  ``at`` says where the cells sit in the plan:
+    an int, the position of the first of a range, or an int64 array with every cell's position.  ``presented``: row i of
+    ``counts`` is cell ``perm[i]`` of those given; else ``perm`` is None and the rows are the cells as given.  ``check``:
+    the sampler's ``check_domain``; ``token``: its ``means_token``."""
+    ranged = np.ndim(at) == 0
+    perm, index = None, None if ranged else at
+    if presented:
+        # The cells are PRESENTED to the sampler grouped by their row of the mean tensor (every count is keyed by the cell's
+        # position in the plan -- cell_index --, so the matrix is the same whatever the order): the kernel then finds a gene
+        # tile's rows of the mean tensor in cache instead of fetching them once per cell, 2 to 5 % of its time
+        # (profiles/r05_ablation.txt).  The device matrix is in the order of presentation; the copy to the host puts the rows
+        # back in plan order chunk by chunk (a gather on the device, under the transfer of the previous chunk).
+        perm = _device.plan_order(rows, means.shape[0])
+        rows, scalings = rows[perm], scalings[perm]
+        index = at + perm.astype(np.int64) if ranged else at[perm]
+    counts = ctx.sample_counts(means, rows, scalings, alpha, beta, seed=seed, cell_offset=at if index is None else 0,
+                               cell_index=index, check_domain=check, means_token=token)
+    return counts, perm
+
+
+class _DeferredVerdict:
+    """The protocol of the deferred domain check, for a call that makes one or more checked launches:
+
+        with _DeferredVerdict(ctx, strict) as verdict:
+            ctx.sample_counts(..., check_domain=verdict.mode)       # "deferred", or False without ``strict``
+            verdict.enqueued()
+
+    The check rides in the call's own kernels and is not waited for; its verdict is sticky in the ctx and covers every
+    launch enqueued so far (in a pipeline an invalid chunk i + 1 may already be reported with chunk i: the plan is one
+    call).  Once a checked launch is enqueued, its verdict is read (``ctx.domain_status()``: raises it) before the block is
+    left normally, and read and discarded when the block is left in any other way -- an exception of a later launch, of the
+    host copy (the OverflowError of "numpy16", a failed page-lock) or of a transfer, the consumer dropping a generator --
+    so that no verdict outlives its call to be raised by an unrelated later one.  ``read()`` reads it earlier."""
+
+    def __init__(self, ctx, strict):
+        self.ctx, self.mode, self.open = ctx, "deferred" if strict else False, False
+
+    def enqueued(self):
+        self.open = bool(self.mode)
+
+    def read(self, still_open=False):
+        """Raise the verdict of the launches so far; ``still_open``: a launch is already enqueued behind what was waited for."""
+        if self.mode:
+            self.ctx.domain_status()
+            self.open = still_open
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, traceback):
+        if self.open and exc_type is None:
+            self.read()
+        elif self.open:
+            _discard_verdict(self.ctx)
 
 
 def _discard_verdict(ctx):
@@ -649,8 +682,7 @@ def add_non_diff_genes(inform_expr_matrix, genes, gene_params, cell_scalings, *,
     with one constant mean row; returns float64 like the reference.  ``strict``: as in ``draw_counts``."""
     N, G = inform_expr_matrix.shape
     if seed is None:
-        lo, hi = random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
-        seed = int(lo) | (int(hi) << 32)
+        seed = _default_seed()
     ctx = _device.get_context()
     base = np.asarray(gene_params["base_expr"], dtype=np.float64).reshape(1, genes)
     extra = ctx.sample_counts(base.astype(np.float32), np.zeros(N, dtype=np.int32),

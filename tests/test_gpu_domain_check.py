@@ -530,6 +530,7 @@ def test_draw_counts_sees_an_edited_mean_in_every_return_form(how):
 def test_plan_drawing_entry_points_raise_and_leave_nothing_behind():
     from oracle import ref_numpy
     from prosstt_amd import device
+    from prosstt_amd import parallel
     from prosstt_amd import simulation as sim
     from prosstt_amd import summary
     ctx = device.get_context()
@@ -547,6 +548,10 @@ def test_plan_drawing_entry_points_raise_and_leave_nothing_behind():
     cells, chunk = 20, 7
     density = seeded(lambda strict: sim.sample_density(t, cells, alpha=al, beta=be, seed=3, out="numpy32", strict=strict))
     chunks = seeded(lambda strict: list(sim.sample_density_chunks(t, cells, chunk, alpha=al, beta=be, seed=3, strict=strict)))
+    # (no process group: the one rank owns every cell)
+    sharded = seeded(lambda strict: parallel.sample_density_sharded(t, cells, alpha=al, beta=be, seed=3, strict=strict))
+    gathered = seeded(lambda strict: parallel.sample_and_gather(t, cells, alpha=al, beta=be, seed=3, chunk_cells=chunk,
+                                                                strict=strict))
     clean, pt, br, sc = density(True)
     rows = sim.cell_rows(t, pt, br)
     stacked = _stacked(t)
@@ -567,6 +572,11 @@ def test_plan_drawing_entry_points_raise_and_leave_nothing_behind():
         assert got[0][n, 11] == 0 and np.array_equal(np.delete(got[0], n, axis=0), np.delete(clean, n, axis=0))
         parts = _strict_and_not(ctx, chunks)
         assert np.array_equal(np.concatenate([p[0] for p in parts]), got[0])
+        # the same plan (same numpy seed, same draws) through the sharded pair and the pipeline, brought to plan order
+        counts, mine = _strict_and_not(ctx, sharded)[:2]
+        assert np.array_equal(parallel.gather_rows(counts, mine, cells).cpu().numpy(), got[0])
+        full, cell_of_row = _strict_and_not(ctx, gathered)[:2]
+        assert np.array_equal(device.to_plan_order(cell_of_row, full.cpu().numpy())[0], got[0])
         # the chunks that were served before the raise held no refused sample: chunk i + 1 is enqueued before the
         # verdict behind chunk i is read, so the raise comes with the offending chunk or the one before it
         np.random.seed(33)
