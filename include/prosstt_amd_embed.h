@@ -24,6 +24,10 @@
  *  - X: row r, gene g at X[r*ld + g] (unit column stride, row stride ld >= G; any base alignment).  Every entry must be
  *    >= 0; a negative entry sets *status to 1 (the caller zeroes it; it is only ever set) and leaves the outputs
  *    meaningless.
+ *  - inv_size[i] = fl32(1 / s[i]) must lie in [2^-126, 2^94] (2^-94 <= s <= 2^126); the caller checks it (embed.py
+ *    refuses other size factors), the library does not read it on the host.  Below 2^-126 it is a denormal; above
+ *    2^94 the product x * inv_size of a large count overflows (a NaN entry) or exceeds 2^126, where v_rcp_f32 returns 0
+ *    for a denormal reciprocal.  Inside the range every entry is 0 (x = 0) or a normal float32 within 2^-20.
  *  - Limits, refused with PROSSTT_AMD_EMBED_EINVAL: 1 <= N < 2^31, 1 <= G, ld >= G, 1 <= l <= 128, a workspace at least
  *    the query's.
  */

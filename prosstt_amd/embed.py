@@ -17,7 +17,8 @@ torch, with only l x l factors on the host.
     p.scores                                          # (cells, k) in plan order: the input of neighbours / UMAP
 
 The definition.  A[i, j] = log1p(X[i, j] / s[i]) (natural log), formed on the device in float32 with a relative error
-of at most 2^-20.  Genes are centred, Ac = A - 1 mu^T with mu = S1 / N, but Ac is never formed: Ac.W = A.W - 1 (mu^T W)
+of at most 2^-20 for size factors 2^-94 <= s <= 2^126 (inv_size = fl32(1 / s) in [2^-126, 2^94]; others are refused:
+past 2^94 a large count's x * inv_size overflows, or its hardware reciprocal is flushed).  Genes are centred, Ac = A - 1 mu^T with mu = S1 / N, but Ac is never formed: Ac.W = A.W - 1 (mu^T W)
 and Ac^T.Q = A^T.Q - mu (1^T Q) are rank-1 corrections in binary64.  With l = min(k + 10, N, G) and
 Omega = np.random.default_rng(seed).standard_normal((G, l)):
 
@@ -42,6 +43,8 @@ from .device import _torch
 MAX_PANEL = 128                 # l: the widest panel the kernels take
 OVERSAMPLE = 10                 # l = min(k + OVERSAMPLE, N, G)
 MAX_COMPONENTS = MAX_PANEL - OVERSAMPLE
+MIN_INV_SIZE = 2.0 ** -126      # inv_size = fl32(1 / s): the smallest normal float32
+MAX_INV_SIZE = 2.0 ** 94        # x * inv_size < 2^125 for every int32 count x: v_rcp_f32 of it stays a normal float32
 
 
 class PCA(NamedTuple):
@@ -66,7 +69,9 @@ def _counts(counts):
 
 
 def _inverse_sizes(size_factors, n_cells):
-    """fl32(1 / s) of positive, finite host size factors (binary64 division), or raise ValueError."""
+    """fl32(1 / s) of positive, finite host size factors (binary64 division), or raise ValueError.  The kernels' domain
+    of inv_size is [2^-126, 2^94] (include/prosstt_amd_embed.h), that is 2^-94 <= s <= 2^126: past 2^94 a large count's
+    x * inv overflows to a NaN entry, or the reciprocal in log1p's formula is a denormal that the hardware flushes."""
     torch = _torch()
     if isinstance(size_factors, torch.Tensor):
         size_factors = size_factors.detach().cpu().numpy()
@@ -77,8 +82,11 @@ def _inverse_sizes(size_factors, n_cells):
         raise ValueError("size factors must be positive and finite")
     with np.errstate(over="ignore"):
         inv = (1.0 / s).astype(np.float32)
-    if not np.all(np.isfinite(inv)) or not np.all(inv >= np.finfo(np.float32).tiny):
+    if not np.all(np.isfinite(inv)) or not np.all(inv >= MIN_INV_SIZE):
         raise ValueError("size factors must have a normal float32 reciprocal")
+    if not np.all(inv <= MAX_INV_SIZE):
+        raise ValueError("size factors must be at least 2^-94 (the float32 reciprocal of a size factor may not exceed "
+                         "2^94)")
     return inv
 
 
@@ -87,7 +95,8 @@ class LogNormalized:
 
     ``counts``: a (cells, genes) int32 device tensor with unit column stride (any row stride: column slices of a wider
     tensor are fine), or a ``device.PresentedCounts``; ``size_factors``: positive, finite host values, one per cell in
-    plan order (the sampler's scalings, or e.g. cell_total / median).  A ``PresentedCounts`` is read in its row order:
+    plan order (the sampler's scalings, or e.g. cell_total / median) with 2^-94 <= s <= 2^126, so that inv_size =
+    fl32(1 / s) lies in [2^-126, 2^94].  A ``PresentedCounts`` is read in its row order:
     the operator permutes the size factors and the N x l panels (``index_select``), never the matrix.
 
     ``.shape``; ``.gene_moments()`` -> (S1, S2) binary64 numpy sums of A and A^2 per gene; ``.matmul(W)``: f32 device

@@ -200,10 +200,19 @@ def test_library_exports_every_declared_symbol():
             assert hasattr(lib, name), name
 
 
-@pytest.mark.parametrize("bad", ["short", "zero", "negative", "nan", "inf", "tiny"])
+@pytest.mark.parametrize("bad", ["short", "zero", "negative", "nan", "inf", "tiny", "below_domain", "domain_edge"])
 def test_bad_size_factors_are_refused(bad):
     X, s = synthetic(N=20, G=10)
     s = s.copy()
+    if bad == "domain_edge":                                 # s = 2^-94 (inv_size = 2^94) is the smallest accepted:
+        s[3] = 2.0 ** -94                                    # refused only for the matrix being on the CPU
+        with pytest.raises(ValueError, match="device") as e:
+            embed.LogNormalized(torch.as_tensor(X), s)
+        assert "size factor" not in str(e.value)
+        assert embed._inverse_sizes(s, 20)[3] == np.float32(2.0 ** 94)
+        with pytest.raises(ValueError, match="size factor"):
+            embed._inverse_sizes(np.where(np.arange(20) == 3, 2.0 ** -94 * (1 - 2.0 ** -20), s), 20)
+        return
     if bad == "short":
         s = s[:-1]
     elif bad == "zero":
@@ -214,6 +223,8 @@ def test_bad_size_factors_are_refused(bad):
         s[3] = np.nan
     elif bad == "inf":
         s[3] = np.inf
+    elif bad == "below_domain":
+        s[3] = 1e-30                                         # 1 / s is a finite float32 above 2^94: x / s can overflow
     else:
         s[3] = 1e-300                                        # 1 / s overflows float32
     with pytest.raises(ValueError, match="size factor"):

@@ -15,7 +15,8 @@ LS = [1, 7, 32, 64, 100, 128]
 KINDS = ["nb", "big", "zeros"]
 # (N, G, l, pad, shift, kind): every N, G and l at least twice, pads and unaligned bases; the largest pairs kept few
 CASES = [(NS[i % 7], GS[(3 * i + 1) % 7], LS[i % 6], (0, 1, 3, 64)[(i // 3) % 4], (i // 2) % 2, KINDS[i % 3])
-         for i in range(21)] + [(4097, 5003, 64, 0, 0, "nb"), (1000, 1025, 128, 3, 1, "big")]
+         for i in range(21)] + [(4097, 5003, 64, 0, 0, "nb"), (1000, 1025, 128, 3, 1, "big"),
+                                (1000, 1025, 65, 1, 0, "nb"), (65, 5003, 96, 3, 1, "big")]      # lp = 96: NT = 3
 
 
 def _matrix(N, G, pad, shift, kind, seed):
