@@ -97,10 +97,20 @@ LIBRARIES = {
         "prosstt_amd_knn_workspace_bytes": _int(i64, i64, i64, i64, _ptr_to(u64)),
         "prosstt_amd_knn_search": _int(vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, u64),
     }, "prosstt_amd_knn_last_error"),
+    # include/prosstt_amd_graph.h: connectivities of the kNN graph and its diffusion operator
+    "graph": _Library(_path("PROSSTT_AMD_GRAPH_LIB", "libprosstt_amd_graph.so"), "prosstt_amd/csrc/graph", True, {
+        "prosstt_amd_graph_last_error": _text,
+        "prosstt_amd_graph_workspace_bytes": _int(i64, i64, _ptr_to(u64)),
+        "prosstt_amd_graph_memberships": _int(vp, vp, vp, i64, i64, vp, vp, vp, vp),
+        "prosstt_amd_graph_symmetrize_emit": _int(vp, vp, vp, i64, i64, vp, u64),
+        "prosstt_amd_graph_symmetrize_fold": _int(vp, vp, vp, vp, i64, i64, i64, vp, u64, vp, vp, vp),
+        "prosstt_amd_graph_normalize": _int(vp, vp, vp, vp, i64, i64, vp, vp, vp, vp),
+        "prosstt_amd_graph_spmv": _int(vp, vp, vp, vp, i64, i64, vp, vp, i32),
+    }, "prosstt_amd_graph_last_error"),
 }
 
-LIB_PATH, HOST_LIB_PATH, STATS_LIB_PATH, EMBED_LIB_PATH, KNN_LIB_PATH = (lib.path for lib in LIBRARIES.values())
-SYMBOLS, HOST_SYMBOLS, STATS_SYMBOLS, EMBED_SYMBOLS, KNN_SYMBOLS = (list(lib.symbols) for lib in LIBRARIES.values())
+LIB_PATH, HOST_LIB_PATH, STATS_LIB_PATH, EMBED_LIB_PATH, KNN_LIB_PATH, GRAPH_LIB_PATH = (lib.path for lib in LIBRARIES.values())
+SYMBOLS, HOST_SYMBOLS, STATS_SYMBOLS, EMBED_SYMBOLS, KNN_SYMBOLS, GRAPH_SYMBOLS = (list(lib.symbols) for lib in LIBRARIES.values())
 
 
 class NativeError(RuntimeError):
@@ -173,6 +183,11 @@ def load_knn():
     return _load("knn")
 
 
+def load_graph():
+    """libprosstt_amd_graph.so (include/prosstt_amd_graph.h), once.  Raises if it has not been built."""
+    return _load("graph")
+
+
 def check(code):
     _check("sampler", code)
 
@@ -187,6 +202,10 @@ def check_embed(code):
 
 def check_knn(code):
     _check("knn", code)
+
+
+def check_graph(code):
+    _check("graph", code)
 
 
 def device_count():
