@@ -111,6 +111,24 @@ int prosstt_amd_sample_counts(prosstt_amd_ctx* ctx, const float* means, int64_t 
 int prosstt_amd_plan_order(const int32_t* row_of_cell, int64_t N, int64_t rows, int32_t* order);
 
 /*
+ * Where the presented cells share rows of the mean tensor (host helper, no device work): the word the preparation kernel
+ * of prosstt_amd_sample_counts writes into every cell's record for a launch whose waves take `strip_cells` cells each.
+ * A run is a stretch of consecutive cells of one strip on the same row (a row outside [0, rows) counts as the nearest
+ * row, as in the kernels).  words[i], i < N: a run's first cell carries the run's length in its low 16 bits, a strip's
+ * first cell also the number of runs of its strip in its high 16 bits, every other cell 0; words[N .. N+3] = 1.  A wave
+ * whose strip has runs * 8 <= cells loads a mean segment once per run instead of once per cell.  `words` holds N + 4
+ * entries; HOST arrays.
+ */
+int prosstt_amd_run_plan(const int32_t* row_of_cell, int64_t N, int64_t rows, int32_t strip_cells, uint32_t* words);
+
+/*
+ * The same words as the preparation kernel of the LAST prosstt_amd_sample_counts call on this ctx wrote them (N + 4 of
+ * them; at most `cap` are copied, *total receives their number, *strip_cells the strip length of that launch).  For
+ * tests and diagnostics: it synchronises and copies.  Valid until the next call on the ctx.
+ */
+int prosstt_amd_last_run_plan(prosstt_amd_ctx* ctx, uint32_t* words, int64_t cap, int64_t* total, int32_t* strip_cells);
+
+/*
  * The verdict of the PROSSTT_AMD_CHECK_DEFERRED calls since the last time, read and cleared (synchronises the stream):
  * *status = 0, PROSSTT_AMD_EDOMAIN (a mean that is not positive and finite, or alpha*m + beta < 1: where scipy's argument check behind
  * simulation.py:647-648 raises ValueError) or PROSSTT_AMD_EINVAL (a row index outside the mean tensor); the message is in

@@ -49,6 +49,8 @@ LIBRARIES = {
         "prosstt_amd_sample_counts": _int(vp, vp, i64, i32, vp, vp, vp, vp, i64, u64, u64, vp, vp, i64, u32),
         "prosstt_amd_plan_order": _int(vp, i64, i64, vp),
         "prosstt_amd_last_list": _int(vp, vp, vp, i64, _ptr_to(i64), _ptr_to(i32)),
+        "prosstt_amd_run_plan": _int(vp, i64, i64, i32, vp),
+        "prosstt_amd_last_run_plan": _int(vp, vp, i64, _ptr_to(i64), _ptr_to(i32)),
         "prosstt_amd_nb_params": _int(vp, vp, i64, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, u32),
         "prosstt_amd_hw_math": _int(vp, i32, u32, u64, vp, u32),
         "prosstt_amd_hw_math_at": _int(vp, i32, vp, u64, vp, u32),

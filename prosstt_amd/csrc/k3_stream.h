@@ -9,9 +9,16 @@
 //   ~33 % then walk the pmf for k >= 1 (data-dependent length, half of them end at k <= 2);
 //   ~0.1 % need gamma-Poisson.
 // Run lane-per-sample, every wave pays for its slowest lane in every one of these.  Here
-//   stage 1 (uniform)   one count-matrix row segment per wave pass: 16-B mean load, one
-//                       Philox call per lane, the bound test as a compare mask; survivors are
-//                       pushed on stack S1 under exec = mask;
+//   stage 1 (uniform)   one count-matrix row segment per wave pass: one Philox call per lane, the bound
+//                       test as a compare mask; survivors are pushed on stack S1 under exec = mask.  The
+//                       16-B mean segment of a lane is loaded once per RUN of cells of the strip that sit on
+//                       one row of the mean tensor (the run loop: cells arrive grouped by row from
+//                       simulation.draw_counts, 125 to a row on the headline workload, and between two run
+//                       boundaries a pass has no vector-memory load, no hand-over of segments and no wait on
+//                       vmcnt), or -- a strip whose cells change rows all the time -- once per cell, two
+//                       cells ahead (the per-cell loop).  Which of the two: once per strip, from the first
+//                       cell's record (CellInfo::runs, run_word; -3.9 % of the kernel on the headline
+//                       workload, -4.1 % on T32: profiles/r11_ablation.txt);
 //   stage 2 (64 of S1)  P(X = 0) and the class test, then the terms k = 0 .. 4 (PRNB-7; 0 .. 2 until round 5: a quarter of
 //                       the walks that reached stage 3 ended within two more terms); what is still
 //                       undecided is pushed on S2 with the pmf state at k = 5;
@@ -76,8 +83,40 @@ constexpr int kInvTab = 272;       // 1/k for k < 272: the reciprocals a pass at
 // row of the count matrix: ph[0] = cell_hi ^ k0, ph[1] = hi(M1 * (hi(M0 * cell_lo) ^ k1)) ^ (k0 + W0),
 // ph[2] = lo(M0 * cell_lo) ^ (k1 + W1), ph[3] = lo(M1 * (hi(M0 * cell_lo) ^ k1))  (philox_cell_part).
 // The array holds N + 4 entries (the last cell repeated) so that prefetches need no clamp.
-struct CellInfo { uint64_t row_bytes; float s; uint32_t reserved; uint32_t ph[4]; };
+// `runs` says where the cells of a strip share a row (run_word, below): the strip loop reads it at a run's first cell.
+struct CellInfo { uint64_t row_bytes; float s; uint32_t runs; uint32_t ph[4]; };
 static_assert(sizeof(CellInfo) == 32, "one s_load_dwordx8");
+
+// A strip whose cells share rows in runs of at least kRunMinCells on average loads a mean segment once per run, not once
+// per cell (the run loop of the stream kernel): runs * kRunMinCells <= cells, decided once per strip.
+constexpr int kRunMinCells = 8;
+
+// CellInfo::runs of entry i of a call of N cells in strips of `strip_cells`.  A run is a stretch of consecutive cells
+// of one strip on the same (clamped, as the preparation kernel clamps it) row of the mean tensor.  The first cell of a
+// run carries the run's length in its low 16 bits -- it ends with the strip and with N --, a strip's first cell also the
+// number of runs of the strip in its high 16 bits; every other cell carries 0, and the four entries behind the last
+// cell carry 1 (a run loop's read-ahead may land there).  At most strip_cells reads of row_of_cell, by a run's first
+// cell only.
+__host__ __device__ inline uint32_t run_word(const int32_t* row_of_cell, int64_t i, int64_t N, int64_t rows, int32_t strip_cells)
+{
+    if (i >= N) return 1u;
+    auto row = [&](int64_t n) -> int64_t { const int64_t r = row_of_cell[n]; return r < 0 ? 0 : (r >= rows ? rows - 1 : r); };
+    const int64_t first = i - i % strip_cells;
+    const int64_t end = first + strip_cells < N ? first + strip_cells : N;
+    const int64_t mine = row(i);
+    if (i != first && row(i - 1) == mine) return 0u;
+    int64_t j = i + 1;
+    while (j < end && row(j) == mine) ++j;
+    const uint32_t len = (uint32_t)(j - i);
+    if (i != first) return len;
+    uint32_t runs = 1u;
+    for (int64_t prev = mine; j < end; ++j) {
+        const int64_t r = row(j);
+        runs += r != prev;
+        prev = r;
+    }
+    return len | (runs << 16);
+}
 
 constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u, kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
 
@@ -538,8 +577,8 @@ __global__ __launch_bounds__(kBlock, 5) void sample_counts_stream_kernel(
 
     // ---- stage 1 over the strip ----------------------------------------------------------------
     // What a pass needs per cell is wave-uniform and arrives by scalar loads issued one pass (the
-    // row offset: three passes) earlier; the mean segments are loaded two cells ahead.  Nothing
-    // is waited for inside the pass that needs it.
+    // row offset of the per-cell loop: three passes) earlier; the mean segments are loaded two cells
+    // (the run loop: one run) ahead.  Nothing is waited for inside the pass that needs it.
     static_assert(kStripCells == 128, "pos keeps the cell in 7 bits above the gene's 8");
     const CellInfo* cinfo = cellinfo + n0;                   // wave-uniform running pointers
     const uint32_t lane4 = (uint32_t)lane * 4u;
@@ -565,8 +604,15 @@ __global__ __launch_bounds__(kBlock, 5) void sample_counts_stream_kernel(
         }
         return r;
     };
-    Seg cur = load_seg(cinfo[0].row_bytes), nxt = load_seg(cinfo[1].row_bytes);
-    uint64_t row2 = cinfo[2].row_bytes;
+    // (which of the two loops below the strip takes: wave-uniform, from the first cell's record -- CellInfo::runs)
+    const uint32_t runs_word = cinfo[0].runs;
+    const bool by_runs = (runs_word >> 16) * (uint32_t)kRunMinCells <= (uint32_t)cells;
+    Seg cur = load_seg(cinfo[0].row_bytes), nxt;
+    uint64_t row2 = 0u;
+    if (!by_runs) {
+        nxt = load_seg(cinfo[1].row_bytes);
+        row2 = cinfo[2].row_bytes;
+    }
     float s = cinfo[0].s;
     uint32_t ph[4] = {cinfo[0].ph[0], cinfo[0].ph[1], cinfo[0].ph[2], cinfo[0].ph[3]};
     const uint64_t quad_p1 = (uint64_t)kPhiloxM1 * ((uint32_t)g0 >> 2);     // the gene quad's part of round 1
@@ -579,8 +625,12 @@ __global__ __launch_bounds__(kBlock, 5) void sample_counts_stream_kernel(
     // the pass (-0.6 %: profiles/r04_ablation.txt).  Every reader masks (the ring address, the late list's shift) or
     // compares against a bound that carries the same 2^23 (flushed_pos); the list for K3h gets the low 16 bits.
     float posf = __uint_as_float(kPosMagic | lane4);
-#pragma unroll 1
-    for (int cl = 0; cl < cells; ++cl) {
+    int cl = 0;
+    // One pass of stage 1 over cell cl of the strip, in two forms: kLoad = the pass loads the mean segment of the cell two
+    // ahead and hands the segments on (a strip whose cells change rows all the time); !kLoad = the cell is on the row of
+    // `cur` like the one before it, and the pass has no vector-memory load, no hand-over and no wait on vmcnt.
+    auto stage1_pass = [&](auto load_tag) {
+        constexpr bool kLoad = decltype(load_tag)::value;
         // every lane runs the whole pass: the stack tops must stay wave-uniform, so no ballot
         // may sit under a divergent branch
         const float m4[4] = {cur.x * s, cur.y * s, cur.z * s, cur.w * s};
@@ -594,8 +644,12 @@ __global__ __launch_bounds__(kBlock, 5) void sample_counts_stream_kernel(
         // place, into the registers this pass has just finished with, saves the ten moves of the rotation
         // below and is 4-5 % slower -- profiles/r04_ablation.txt, inplace1.)
         __builtin_amdgcn_sched_barrier(0);
-        const Seg nn = load_seg(row2);
-        const uint64_t row3 = cinfo[3].row_bytes;
+        Seg nn;
+        uint64_t row3 = 0u;
+        if constexpr (kLoad) {
+            nn = load_seg(row2);
+            row3 = cinfo[3].row_bytes;
+        }
         const float s_next = cinfo[1].s;
         const uint32_t ph_next[4] = {cinfo[1].ph[0], cinfo[1].ph[1], cinfo[1].ph[2], cinfo[1].ph[3]};
         ++cinfo;
@@ -655,12 +709,37 @@ __global__ __launch_bounds__(kBlock, 5) void sample_counts_stream_kernel(
                 while (s2_top >= kS2Run) stage3_pass();
             }
         }
-        cur = nxt;
-        nxt = nn;
-        row2 = row3;
+        if constexpr (kLoad) {
+            cur = nxt;
+            nxt = nn;
+            row2 = row3;
+        }
         s = s_next;
         ph[0] = ph_next[0]; ph[1] = ph_next[1]; ph[2] = ph_next[2]; ph[3] = ph_next[3];
         posf += 256.0f;
+    };
+    if (!by_runs) {
+#pragma unroll 1
+        for (; cl < cells; ++cl) stage1_pass(std::true_type{});
+    } else {
+        // The run loop.  At a run's first cell the record of the cell behind the run (its index is at most N: the array
+        // has four more entries) says where the next run's means are and how long it is; its segment is loaded during
+        // the run's passes and handed over behind them.  The last run of a strip loads a segment that nobody uses.
+        // (A run ends with the strip by the rule of run_word; the clamps keep a record that broke the rule from
+        // reading behind the records or running the loop on: lengths are data.  The record is waited for at once --
+        // it is one scalar load per run.)
+        int run = (int)(runs_word & 0xffffu);
+#pragma unroll 1
+        while (cl < cells) {
+            const int run_end = run > 0 && cl + run < cells ? cl + run : cells;
+            const int len = run_end - cl;
+            nxt = load_seg(cinfo[len].row_bytes);
+            run = (int)(cinfo[len].runs & 0xffffu);
+#pragma unroll 1
+            for (; cl < run_end; ++cl) stage1_pass(std::false_type{});
+            __builtin_amdgcn_s_waitcnt(0x0F70);              // vmcnt(0): the next run's segment (and the rows stored meanwhile)
+            cur = nxt;
+        }
     }
 
     // ---- drain ------------------------------------------------------------------------------------

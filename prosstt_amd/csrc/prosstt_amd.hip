@@ -1,8 +1,9 @@
 // libprosstt_amd.so -- HIP kernels (gfx950) and the C ABI of include/prosstt_amd.h.
 //
 // Kernels
-//   prep_kernel             binary64 scaling/alpha/beta -> binary32 sampler parameters, per-cell records, flag words,
-//                           the per-cell / per-gene part of the domain check
+//   prep_kernel             binary64 scaling/alpha/beta -> binary32 sampler parameters, per-cell records (with the run
+//                           words of k3::run_word: where the cells of a strip share a row), flag words, the per-cell /
+//                           per-gene part of the domain check
 //   k3::sample_counts_stream_kernel + k3::sample_counts_heavy_kernel (k3_stream.h, k3_heavy.h)
 //                           K3: fused gather * scale -> get_pr_umi -> NB draw
 //                           (simulation.py:602-651, count_model.py:131-161)
@@ -23,7 +24,8 @@
 // Host side, each decision in one place
 //   ScratchWord             the words of the ctx's device scratch
 //   Staging                 a call's arrays that may be host pointers (PROSSTT_AMD_HOST_INPUTS / _OUTPUT)
-//   stream_geometry         launch geometry and list capacities of a sample_counts call
+//   stream_geometry         launch geometry and list capacities of a sample_counts call (PROSSTT_AMD_STRIP_CELLS, for
+//                           tests and tools, sets the strip length)
 //   stream_workspace        the regions of its workspace: their sizes and their addresses
 //   sampler_setup           the common front end of sample_counts and nb_params
 #include <hip/hip_runtime.h>
@@ -86,6 +88,8 @@ struct prosstt_amd_ctx {
     k3::HeavyList list{};        // (list.seg_cnt == nullptr: none)
     uint64_t list_regions = 0;
     int64_t list_groups = 0, list_strip_cells = 0;
+    const k3::CellInfo* list_info = nullptr;   // that call's cell records (N + 4 of them), for prosstt_amd_last_run_plan
+    int64_t list_cells = 0;
     int heavy_grid = 1280;       // blocks of K3h that are resident at once on this device (5 per CU: its 30 496 B of LDS)
     // domain check: one byte per row of the mean tensor last scanned ("has an entry that is not in (0, inf)"), and which tensor that was
     uint8_t* row_bad = nullptr;
@@ -185,7 +189,8 @@ struct Staging {
 
 // One launch prepares a sample_counts call: binary64 scaling/alpha/beta -> the binary32 sampler
 // parameters (and the zero-test factor), the per-cell records of the streaming kernel (k3::CellInfo;
-// N + 4 entries, the last cell repeated; skipped when `info` is NULL), and the call's flag words.
+// N + 4 entries, the last cell repeated; skipped when `info` is NULL; `strip_cells`: the strip length of the launch they
+// are for, which their run words depend on), and the call's flag words.
 // With `row_bad` (a checked call) it is also the per-cell and per-gene part of the domain check: scipy's argument
 // check in the reference fails iff some mean m = M*s is not a positive finite number (zero, negative, infinite, NaN) or
 // some theta = a*m + b - 1 is < 0.  The first is decided factor by factor, so that no product can hide it: a scaling
@@ -202,7 +207,7 @@ __global__ void prep_kernel(const double* __restrict__ scaling, int64_t N,
                             const int64_t* __restrict__ cell_index,
                             uint32_t k0, uint32_t k1, k3::CellInfo* __restrict__ info, int64_t* __restrict__ flags,
                             const uint8_t* __restrict__ row_bad, uint32_t parity, k3::HeavyList heavy,
-                            k3::HeavyList* __restrict__ heavy_rec)
+                            k3::HeavyList* __restrict__ heavy_rec, int32_t strip_cells)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (heavy_rec && i < k3::kSegs + 2) heavy.seg_cnt[i] = 0u;      // the fill of the dense lists K3h reads
@@ -228,17 +233,45 @@ __global__ void prep_kernel(const double* __restrict__ scaling, int64_t N,
         phi_f[i] = prnb::zero_test_factor(a, bm1);
         if (row_bad && (!(a >= 0.0f) || !(bm1 >= 0.0f))) flags[kFullReq + parity] = 1;
     }
-    if (info && i < N + 4) {
+    if (info) {
         const int64_t n = i < N ? i : N - 1;
-        const uint64_t cell = cell_index ? (uint64_t)cell_index[n] : cell_offset + (uint64_t)n;
-        k3::CellInfo c;
         // an index outside the tensor (the caller's bug; the checked mode reports it) must not become a wild read
-        const int64_t row = row_of_cell[n] < 0 ? 0 : (row_of_cell[n] >= rows ? rows - 1 : row_of_cell[n]);
-        c.row_bytes = (uint64_t)row * (uint64_t)G * 4u;
-        c.s = (float)scaling[n];
-        c.reserved = 0u;
-        k3::philox_cell_part((uint32_t)cell, (uint32_t)(cell >> 32), k0, k1, c.ph);
-        info[i] = c;
+        auto clamped = [&](int32_t r) -> int64_t { return r < 0 ? 0 : (r >= rows ? rows - 1 : (int64_t)r); };
+        // Everything a record is made of is read here, in one trip to memory, and the empty asm statement keeps the reads
+        // here: the compiler otherwise moves the read of the cell before this one behind the first use of the others,
+        // into the branch that needs it, and the kernel -- as long as its launch -- is one more trip to memory long.
+        int32_t row_here = row_of_cell[n], row_before = row_of_cell[n > 0 ? n - 1 : 0];
+        const uint64_t cell = cell_index ? (uint64_t)cell_index[n] : cell_offset + (uint64_t)n;
+        const float s_n = (float)scaling[n];
+        asm volatile("" : "+v"(row_here), "+v"(row_before));
+        const int64_t row = clamped(row_here);
+        // Where the cells of a strip share a row (k3::run_word, the rule; CellInfo::runs).  A strip length that divides 64
+        // puts every strip inside one wave of this kernel (a block is four whole waves, i = lane mod 64), and the words
+        // come from two lane masks -- who starts a run, who is a cell -- with one more read of row_of_cell per thread:
+        // reading on to the run's end, one dependent load after the other, costs a strip's worth of load latencies in a
+        // kernel that is otherwise as long as its launch.
+        uint32_t word;
+        if (strip_cells > 0 && 64 % strip_cells == 0) {               // (every thread of the wave comes by here)
+            const uint32_t lane = threadIdx.x & 63u, pos = lane & (uint32_t)(strip_cells - 1), first = lane - pos;
+            const bool cell_here = i < N;
+            const bool starts_run = cell_here && (pos == 0u || clamped(row_before) != row);
+            const unsigned long long strip_m = (strip_cells == 64 ? ~0ull : (1ull << strip_cells) - 1ull) << first;
+            const unsigned long long starts_m = __builtin_amdgcn_ballot_w64(starts_run) & strip_m;
+            const unsigned long long cells_m = __builtin_amdgcn_ballot_w64(cell_here) & strip_m;
+            const unsigned long long behind = starts_m & ~((2ull << lane) - 1ull);      // the runs that start behind this lane
+            const uint32_t end = behind ? (uint32_t)__ffsll((long long)behind) - 1u : first + (uint32_t)__popcll(cells_m);
+            word = !cell_here ? 1u : (!starts_run ? 0u : ((end - lane) | (pos == 0u ? (uint32_t)__popcll(starts_m) << 16 : 0u)));
+        } else {
+            word = i < N + 4 ? k3::run_word(row_of_cell, i, N, rows, strip_cells) : 0u;
+        }
+        if (i < N + 4) {
+            k3::CellInfo c;
+            c.row_bytes = (uint64_t)row * (uint64_t)G * 4u;
+            c.s = s_n;
+            c.runs = word;
+            k3::philox_cell_part((uint32_t)cell, (uint32_t)(cell >> 32), k0, k1, c.ph);
+            info[i] = c;
+        }
     }
 }
 
@@ -734,6 +767,12 @@ static StreamGeometry stream_geometry(int64_t N, int32_t G)
     g.strip_cells = k3::kStripCells / 2;    // 64: measured best on C3 (128: +1.7 %, 32: +2.7 %)
     const int64_t n = N > 0 ? N : 0;
     while (g.strip_cells > 8 && ((n + g.strip_cells - 1) / g.strip_cells) * g.tiles_g < 4 * 5 * 1024) g.strip_cells /= 2;
+    // for tests and tools: a small problem with the strips of a large one (PROSSTT_AMD_STRIP_CELLS = 8, 16, 32 or 64, the
+    // lengths the rule above chooses from; anything else is ignored)
+    if (const char* forced = getenv("PROSSTT_AMD_STRIP_CELLS")) {
+        const long v = strtol(forced, nullptr, 10);
+        if (v == 8 || v == 16 || v == 32 || v == 64) g.strip_cells = v;
+    }
     g.strips = (n + g.strip_cells - 1) / g.strip_cells;
     g.groups = (g.strips + 3) / 4;
     g.regions = (uint64_t)(g.groups * g.tiles_g) * 4u;
@@ -854,7 +893,7 @@ static int sampler_setup(prosstt_amd_ctx* c, Staging& st, const float* means, in
     prep_kernel<<<dim3((unsigned)((span + 255) / 256)), dim3(256), 0, c->stream>>>(
         scaling, N, alpha, beta, G, A->scal, A->ga, A->gbm1, A->gphi, row_of_cell, rows, cell_offset, cell_index,
         (uint32_t)seed, (uint32_t)(seed >> 32), A->cellinfo, geo ? c->scratch : nullptr,
-        row_bad, c->call_parity, A->heavy, A->heavy_rec);
+        row_bad, c->call_parity, A->heavy, A->heavy_rec, geo ? (int32_t)geo->strip_cells : 1);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -901,6 +940,35 @@ PA_EXPORT int prosstt_amd_plan_order(const int32_t* row_of_cell, int64_t N, int6
     }
     for (int64_t r = 0; r < rows; ++r) first[(size_t)r + 1] += first[(size_t)r];
     for (int64_t n = 0; n < N; ++n) order[first[(size_t)row_of_cell[n]]++] = (int32_t)n;
+    return 0;
+}
+PA_CATCH
+
+PA_EXPORT int prosstt_amd_run_plan(const int32_t* row_of_cell, int64_t N, int64_t rows, int32_t strip_cells, uint32_t* words) try
+{
+    if (N < 0 || rows < 1 || N > 0x7fffffffll) return fail(PROSSTT_AMD_EINVAL, "bad size");
+    if (strip_cells < 1 || strip_cells > k3::kStripCells) return fail(PROSSTT_AMD_EINVAL, "strip_cells outside [1,%d]", k3::kStripCells);
+    if (!words || (N > 0 && !row_of_cell)) return fail(PROSSTT_AMD_EINVAL, "NULL argument");
+    for (int64_t i = 0; i < N + 4; ++i) words[i] = k3::run_word(row_of_cell, i, N, rows, strip_cells);
+    return 0;
+}
+PA_CATCH
+
+PA_EXPORT int prosstt_amd_last_run_plan(prosstt_amd_ctx* c, uint32_t* words, int64_t cap, int64_t* total, int32_t* strip_cells) try
+{
+    if (!c || !total) return fail(PROSSTT_AMD_EINVAL, "NULL argument");
+    if (cap > 0 && !words) return fail(PROSSTT_AMD_EINVAL, "NULL output array");
+    *total = 0;
+    if (strip_cells) *strip_cells = 0;
+    if (!c->list.seg_cnt || !c->list_info) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *total = c->list_cells + 4;
+    if (strip_cells) *strip_cells = (int32_t)c->list_strip_cells;
+    const int64_t n = cap < *total ? cap : *total;
+    if (n > 0)      // one word of every 32-byte record
+        HIP_TRY(hipMemcpy2D(words, 4, (const char*)c->list_info + offsetof(k3::CellInfo, runs), sizeof(k3::CellInfo), 4, (size_t)n,
+                            hipMemcpyDeviceToHost));
     return 0;
 }
 PA_CATCH
@@ -976,6 +1044,8 @@ PA_EXPORT int prosstt_amd_sample_counts(prosstt_amd_ctx* c, const float* means, 
     c->list_regions = geo.regions;
     c->list_groups = geo.groups;
     c->list_strip_cells = geo.strip_cells;
+    c->list_info = cellinfo;
+    c->list_cells = N;
     c->call_parity ^= 1u;
     if (st.host_out)   // G columns of every row; the caller's padding beyond G is left alone
         HIP_TRY(hipMemcpy2DAsync(out, (size_t)ld_out * 4, d_out, (size_t)ld_out * 4, (size_t)G * 4, (size_t)N,

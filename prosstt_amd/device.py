@@ -164,6 +164,17 @@ class Context:
         n = min(cap, total.value)
         return cells[:n], genes[:n], total.value, bool(over.value)
 
+    def last_run_plan(self):
+        """(words, strip_cells): the run words of the cell records of the last sample_counts call (N + 4 of them) and
+        the strip length of its launch (see prosstt_amd_last_run_plan and ``run_plan``)."""
+        total = ctypes.c_int64(0)
+        strip = ctypes.c_int32(0)
+        _native.check(self._lib.prosstt_amd_last_run_plan(self._h, None, 0, ctypes.byref(total), ctypes.byref(strip)))
+        words = np.empty(total.value, np.uint32)
+        _native.check(self._lib.prosstt_amd_last_run_plan(
+            self._h, words.ctypes.data_as(ctypes.c_void_p), words.size, ctypes.byref(total), ctypes.byref(strip)))
+        return words, strip.value
+
     HW_OPS = dict(rcp=0, log2=1, exp2neg=2)
 
     def hw_math(self, op, first_bits, count):
@@ -340,6 +351,18 @@ def plan_order(row_of_cell, rows=None):
         _native.check(_native.load().prosstt_amd_plan_order(
             roc.ctypes.data_as(ctypes.c_void_p), roc.size, n_rows, order.ctypes.data_as(ctypes.c_void_p)))
     return order
+
+
+def run_plan(row_of_cell, rows, strip_cells):
+    """uint32 array of N + 4 words: where cells presented in this order share rows of the mean tensor, as the sampler's
+    preparation kernel records it for waves that take ``strip_cells`` cells each (prosstt_amd_run_plan; host arrays, no
+    device work).  Low 16 bits: the length of the run that starts at the cell (0: none starts there); high 16 bits, at a
+    strip's first cell: the runs of the strip."""
+    roc = np.ascontiguousarray(row_of_cell, dtype=np.int32)
+    words = np.empty(roc.size + 4, dtype=np.uint32)
+    _native.check(_native.load().prosstt_amd_run_plan(
+        roc.ctypes.data_as(ctypes.c_void_p), roc.size, int(rows), int(strip_cells), words.ctypes.data_as(ctypes.c_void_p)))
+    return words
 
 
 def inverse_permutation(perm):

@@ -24,8 +24,8 @@ RUN_23 = """            while (s1_at - s1_lds >= 64u * 16u) {
                 while (s2_top >= kS2Run) stage3_pass();
             }
         }
-        cur = nxt;"""
-S1_ONLY = (RUN_23, "            s1_at = s1_lds;\n        }\n        cur = nxt;")
+        if constexpr (kLoad) {"""
+S1_ONLY = (RUN_23, "            s1_at = s1_lds;\n        }\n        if constexpr (kLoad) {")
 
 PHILOX_OFF = ("        const prnb::Words W = philox_count_row(ph, quad_hi, quad_lo, k0, k1);",
               "        prnb::Words W; W.w[0] = (ph[0] * 2654435761u) ^ ((uint32_t)g0 * 40503u); W.w[1] = W.w[0] * 3u + k0;\n"
@@ -45,7 +45,7 @@ VARIANTS = {
     # stage 1 only: survivors are pushed, then dropped
     "s1": [S1_ONLY],
     # stages 1 + 2: what stage 2 pushes on S2 is dropped
-    "s12": [(RUN_23, "            while (s1_at - s1_lds >= 64u * 16u) { stage2_pass(std::true_type{}); s2_top = 0; }\n        }\n        cur = nxt;")],
+    "s12": [(RUN_23, "            while (s1_at - s1_lds >= 64u * 16u) { stage2_pass(std::true_type{}); s2_top = 0; }\n        }\n        if constexpr (kLoad) {")],
     # stage 1 without the Philox call (a 2-instruction hash stands in)
     "s1_nophilox": [S1_ONLY, PHILOX_OFF],
     # stage 1 only, rows not stored (pure issue time of stage 1)
