@@ -19,6 +19,11 @@ Exact k nearest neighbours of the cells on the device (what ``pp.neighbors`` com
     from prosstt_amd import neighbors
     nb = neighbors.knn(p.scores, 14)                  # nb.indices, nb.sq_distances, nb.distances, nb.to_csr()
 
+The UMAP layout of that neighbour graph on the device (what ``tl.umap`` computes, in a reproducible form):
+
+    from prosstt_amd import layout
+    lay = layout.umap(nb)                             # lay.embedding (cells, 2) float32
+
 or, for unmodified scripts that say ``from prosstt import ...``:
 
     import prosstt_amd; prosstt_amd.install_as_prosstt()

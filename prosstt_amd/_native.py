@@ -34,7 +34,7 @@ def _int(*argtypes):
 
 _ptr_to = ctypes.POINTER
 _text = (ctypes.c_char_p, None)
-vp, i32, i64, u32, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64
+vp, i32, i64, u32, u64, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double
 _widen = _int(vp, vp, u64, i32)
 
 LIBRARIES = {
@@ -109,10 +109,16 @@ LIBRARIES = {
         "prosstt_amd_graph_normalize": _int(vp, vp, vp, vp, i64, i64, vp, vp, vp, vp),
         "prosstt_amd_graph_spmv": _int(vp, vp, vp, vp, i64, i64, vp, vp, i32),
     }, "prosstt_amd_graph_last_error"),
+    # include/prosstt_amd_layout.h: the epochs of a UMAP layout of the connectivity graph
+    "layout": _Library(_path("PROSSTT_AMD_LAYOUT_LIB", "libprosstt_amd_layout.so"), "prosstt_amd/csrc/layout", True, {
+        "prosstt_amd_layout_last_error": _text,
+        "prosstt_amd_layout_epochs": _int(vp, vp, vp, vp, i64, i64, i32, vp, vp, i32, i32, i32, f64, f64, f64, f64, i32, u64, i32),
+        "prosstt_amd_layout_negatives": _int(vp, u64, i32, i64, i64, i32, i64, vp),
+    }, "prosstt_amd_layout_last_error"),
 }
 
-LIB_PATH, HOST_LIB_PATH, STATS_LIB_PATH, EMBED_LIB_PATH, KNN_LIB_PATH, GRAPH_LIB_PATH = (lib.path for lib in LIBRARIES.values())
-SYMBOLS, HOST_SYMBOLS, STATS_SYMBOLS, EMBED_SYMBOLS, KNN_SYMBOLS, GRAPH_SYMBOLS = (list(lib.symbols) for lib in LIBRARIES.values())
+LIB_PATH, HOST_LIB_PATH, STATS_LIB_PATH, EMBED_LIB_PATH, KNN_LIB_PATH, GRAPH_LIB_PATH, LAYOUT_LIB_PATH = (lib.path for lib in LIBRARIES.values())
+SYMBOLS, HOST_SYMBOLS, STATS_SYMBOLS, EMBED_SYMBOLS, KNN_SYMBOLS, GRAPH_SYMBOLS, LAYOUT_SYMBOLS = (list(lib.symbols) for lib in LIBRARIES.values())
 
 
 class NativeError(RuntimeError):
@@ -190,6 +196,11 @@ def load_graph():
     return _load("graph")
 
 
+def load_layout():
+    """libprosstt_amd_layout.so (include/prosstt_amd_layout.h), once.  Raises if it has not been built."""
+    return _load("layout")
+
+
 def check(code):
     _check("sampler", code)
 
@@ -208,6 +219,10 @@ def check_knn(code):
 
 def check_graph(code):
     _check("graph", code)
+
+
+def check_layout(code):
+    _check("layout", code)
 
 
 def device_count():
