@@ -1,6 +1,6 @@
 """
 ctypes binding of libprosstt_amd.so (include/prosstt_amd.h) and of the libraries beside it: each is described once in
-LIBRARIES, and _load / _check do the rest.
+LIBRARIES, and load / check do the rest.
 
 There is NO CPU fallback: if the library is missing, or no gfx950 device is
 visible, every numeric entry point of the package raises.  torch is used only
@@ -17,11 +17,12 @@ OK, EINVAL, EDOMAIN, EHIP, ENOMEM, ENODEV, ERCCL = 0, -1, -2, -3, -4, -5, -6
 HOST_INPUTS, HOST_OUTPUT, CHECK_DOMAIN, TIME_KERNEL, CHECK_DEFERRED, MEANS_CACHED, PARAMS_NONNEG = 1, 2, 4, 8, 16, 32, 64
 STATS_ACCUMULATE = 1
 
-# One shared library: ``path`` (its environment variable overrides the file in lib/), ``make_dir`` (what builds it),
-# ``hip`` (it runs on the device: torch is imported before it, and there is no CPU fallback for it), ``symbols`` (every
-# symbol its header declares -> (restype, argtypes or None for "not declared here")), ``last_error`` (the symbol that
-# returns the message of a failed call, or None).
-_Library = namedtuple("_Library", "path make_dir hip symbols last_error")
+# One shared library, by the name of its row in prosstt_amd/csrc/Makefile: ``path`` (its environment variable overrides
+# the file in lib/), ``header`` (the file under include/ that declares it), ``hip`` (it runs on the device: torch is
+# imported before it, and there is no CPU fallback for it), ``symbols`` (every symbol its header declares -> (restype,
+# argtypes or None for "not declared here")), ``last_error`` (the symbol that returns the message of a failed call, or
+# None).
+_Library = namedtuple("_Library", "path header hip symbols last_error")
 
 
 def _path(env, filename):
@@ -38,7 +39,7 @@ vp, i32, i64, u32, u64, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, c
 _widen = _int(vp, vp, u64, i32)
 
 LIBRARIES = {
-    "sampler": _Library(_path("PROSSTT_AMD_LIB", "libprosstt_amd.so"), "prosstt_amd/csrc", True, {     # include/prosstt_amd.h
+    "sampler": _Library(_path("PROSSTT_AMD_LIB", "libprosstt_amd.so"), "prosstt_amd.h", True, {
         "prosstt_amd_version": (ctypes.c_int, None),
         "prosstt_amd_last_error": _text,
         "prosstt_amd_device_count": _int(_ptr_to(ctypes.c_int)),
@@ -69,8 +70,8 @@ LIBRARIES = {
         "prosstt_amd_gene_max": _int(vp, vp, i64, i64, vp),
         "prosstt_amd_means_from_rel": _int(vp, vp, vp, i64, i64, vp),
     }, "prosstt_amd_last_error"),
-    # include/prosstt_amd_host.h: host-side helpers, no HIP
-    "host": _Library(_path("PROSSTT_AMD_HOST_LIB", "libprosstt_amd_host.so"), "prosstt_amd/csrc/host", False, {
+    # host-side helpers, no HIP
+    "host": _Library(_path("PROSSTT_AMD_HOST_LIB", "libprosstt_amd_host.so"), "prosstt_amd_host.h", False, {
         "prosstt_amd_host_widen_i32_i64": _widen,
         "prosstt_amd_host_widen_u16_i64": _widen,
         "prosstt_amd_host_widen_u16_i32": _widen,
@@ -79,28 +80,28 @@ LIBRARIES = {
         "prosstt_amd_host_scatter_i32": _int(vp, i32, vp, vp, u64, i32),
         "prosstt_amd_host_has_avx2": (ctypes.c_int, None),
     }, None),
-    # include/prosstt_amd_stats.h: summary statistics of a device count matrix
-    "stats": _Library(_path("PROSSTT_AMD_STATS_LIB", "libprosstt_amd_stats.so"), "prosstt_amd/csrc/stats", True, {
+    # summary statistics of a device count matrix
+    "stats": _Library(_path("PROSSTT_AMD_STATS_LIB", "libprosstt_amd_stats.so"), "prosstt_amd_stats.h", True, {
         "prosstt_amd_stats_last_error": _text,
         "prosstt_amd_stats_workspace_bytes": _int(i64, i64, _ptr_to(u64)),
         "prosstt_amd_stats_count_summary": _int(vp, vp, i64, i64, i64, vp, u64, vp, vp, vp, vp, vp, vp, u32),
     }, "prosstt_amd_stats_last_error"),
-    # include/prosstt_amd_embed.h: products with the log-normalised count matrix
-    "embed": _Library(_path("PROSSTT_AMD_EMBED_LIB", "libprosstt_amd_embed.so"), "prosstt_amd/csrc/embed", True, {
+    # products with the log-normalised count matrix
+    "embed": _Library(_path("PROSSTT_AMD_EMBED_LIB", "libprosstt_amd_embed.so"), "prosstt_amd_embed.h", True, {
         "prosstt_amd_embed_last_error": _text,
         "prosstt_amd_embed_workspace_bytes": _int(i64, i64, i64, _ptr_to(u64)),
         "prosstt_amd_embed_gene_moments": _int(vp, vp, i64, i64, i64, vp, vp, u64, vp, vp, vp),
         "prosstt_amd_embed_matmul": _int(vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, u64, vp),
         "prosstt_amd_embed_rmatmul": _int(vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, u64, vp),
     }, "prosstt_amd_embed_last_error"),
-    # include/prosstt_amd_knn.h: exact k nearest neighbours of the rows of an f32 panel
-    "knn": _Library(_path("PROSSTT_AMD_KNN_LIB", "libprosstt_amd_knn.so"), "prosstt_amd/csrc/knn", True, {
+    # exact k nearest neighbours of the rows of an f32 panel
+    "knn": _Library(_path("PROSSTT_AMD_KNN_LIB", "libprosstt_amd_knn.so"), "prosstt_amd_knn.h", True, {
         "prosstt_amd_knn_last_error": _text,
         "prosstt_amd_knn_workspace_bytes": _int(i64, i64, i64, i64, _ptr_to(u64)),
         "prosstt_amd_knn_search": _int(vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, u64),
     }, "prosstt_amd_knn_last_error"),
-    # include/prosstt_amd_graph.h: connectivities of the kNN graph and its diffusion operator
-    "graph": _Library(_path("PROSSTT_AMD_GRAPH_LIB", "libprosstt_amd_graph.so"), "prosstt_amd/csrc/graph", True, {
+    # connectivities of the kNN graph and its diffusion operator
+    "graph": _Library(_path("PROSSTT_AMD_GRAPH_LIB", "libprosstt_amd_graph.so"), "prosstt_amd_graph.h", True, {
         "prosstt_amd_graph_last_error": _text,
         "prosstt_amd_graph_workspace_bytes": _int(i64, i64, _ptr_to(u64)),
         "prosstt_amd_graph_memberships": _int(vp, vp, vp, i64, i64, vp, vp, vp, vp),
@@ -109,17 +110,13 @@ LIBRARIES = {
         "prosstt_amd_graph_normalize": _int(vp, vp, vp, vp, i64, i64, vp, vp, vp, vp),
         "prosstt_amd_graph_spmv": _int(vp, vp, vp, vp, i64, i64, vp, vp, i32),
     }, "prosstt_amd_graph_last_error"),
-    # include/prosstt_amd_layout.h: the epochs of a UMAP layout of the connectivity graph
-    "layout": _Library(_path("PROSSTT_AMD_LAYOUT_LIB", "libprosstt_amd_layout.so"), "prosstt_amd/csrc/layout", True, {
+    # the epochs of a UMAP layout of the connectivity graph
+    "layout": _Library(_path("PROSSTT_AMD_LAYOUT_LIB", "libprosstt_amd_layout.so"), "prosstt_amd_layout.h", True, {
         "prosstt_amd_layout_last_error": _text,
         "prosstt_amd_layout_epochs": _int(vp, vp, vp, vp, i64, i64, i32, vp, vp, i32, i32, i32, f64, f64, f64, f64, i32, u64, i32),
         "prosstt_amd_layout_negatives": _int(vp, u64, i32, i64, i64, i32, i64, vp),
     }, "prosstt_amd_layout_last_error"),
 }
-
-LIB_PATH, HOST_LIB_PATH, STATS_LIB_PATH, EMBED_LIB_PATH, KNN_LIB_PATH, GRAPH_LIB_PATH, LAYOUT_LIB_PATH = (lib.path for lib in LIBRARIES.values())
-SYMBOLS, HOST_SYMBOLS, STATS_SYMBOLS, EMBED_SYMBOLS, KNN_SYMBOLS, GRAPH_SYMBOLS, LAYOUT_SYMBOLS = (list(lib.symbols) for lib in LIBRARIES.values())
-
 
 class NativeError(RuntimeError):
     def __init__(self, code, message):
@@ -131,15 +128,15 @@ _loaded = {}
 _lock = threading.Lock()
 
 
-def _load(name):
+def load(name="sampler"):
     """The library ``name`` of LIBRARIES with its prototypes declared (loaded once).  Raises if it has not been built."""
     lib = LIBRARIES[name]
     with _lock:
         if name not in _loaded:
             if not os.path.exists(lib.path):
-                raise RuntimeError("%s not found: build it with `make -C %s` (or "
+                raise RuntimeError("%s not found: build it with `make -C prosstt_amd/csrc %s` (or "
                                    "`python -c 'import __graft_entry__ as g; g.build()'`)%s"
-                                   % (lib.path, lib.make_dir, ". prosstt_amd has no CPU fallback." if lib.hip else ""))
+                                   % (lib.path, name, ". prosstt_amd has no CPU fallback." if lib.hip else ""))
             if lib.hip:
                 # torch first: it bundles its own libamdhip64.so.7, and the dynamic loader shares one
                 # copy per SONAME.  Loading ours first would bind torch to /opt/rocm's runtime instead;
@@ -156,73 +153,14 @@ def _load(name):
         return _loaded[name]
 
 
-def _check(name, code):
-    """Raise with the library's message unless ``code`` is OK: NativeError, or ValueError for EDOMAIN (a code of the
-    sampler's ABI alone)."""
+def check(code, name="sampler"):
+    """Raise with the message of library ``name`` unless ``code`` is OK: NativeError, or ValueError for EDOMAIN (a code
+    of the sampler's ABI alone)."""
     if code != OK:
-        msg = getattr(_load(name), LIBRARIES[name].last_error)().decode("utf-8", "replace")
+        msg = getattr(load(name), LIBRARIES[name].last_error)().decode("utf-8", "replace")
         if code == EDOMAIN:
             raise ValueError(msg)          # what scipy raises in the reference (simulation.py:647)
         raise NativeError(code, msg)
-
-
-def load():
-    """libprosstt_amd.so (include/prosstt_amd.h), loaded once.  Raises if it has not been built."""
-    return _load("sampler")
-
-
-def load_host():
-    """libprosstt_amd_host.so (include/prosstt_amd_host.h: host-side helpers, no HIP), once.  Raises if it has not been built."""
-    return _load("host")
-
-
-def load_stats():
-    """libprosstt_amd_stats.so (include/prosstt_amd_stats.h), once.  Raises if it has not been built."""
-    return _load("stats")
-
-
-def load_embed():
-    """libprosstt_amd_embed.so (include/prosstt_amd_embed.h), once.  Raises if it has not been built."""
-    return _load("embed")
-
-
-def load_knn():
-    """libprosstt_amd_knn.so (include/prosstt_amd_knn.h), once.  Raises if it has not been built."""
-    return _load("knn")
-
-
-def load_graph():
-    """libprosstt_amd_graph.so (include/prosstt_amd_graph.h), once.  Raises if it has not been built."""
-    return _load("graph")
-
-
-def load_layout():
-    """libprosstt_amd_layout.so (include/prosstt_amd_layout.h), once.  Raises if it has not been built."""
-    return _load("layout")
-
-
-def check(code):
-    _check("sampler", code)
-
-
-def check_stats(code):
-    _check("stats", code)
-
-
-def check_embed(code):
-    _check("embed", code)
-
-
-def check_knn(code):
-    _check("knn", code)
-
-
-def check_graph(code):
-    _check("graph", code)
-
-
-def check_layout(code):
-    _check("layout", code)
 
 
 def device_count():

@@ -32,6 +32,27 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def need_device(name):
+    """Library ``name`` of _native.LIBRARIES, loaded; RuntimeError unless a device is visible."""
+    L = _native.load(name)
+    if not _torch().cuda.is_available():
+        raise RuntimeError("prosstt_amd needs an AMD MI355X (gfx950) device: there is no CPU fallback")
+    return L
+
+
+def current_stream(dev):
+    """torch's current stream on ``dev``, as the C ABI takes it."""
+    return ctypes.c_void_p(_torch().cuda.current_stream(dev).cuda_stream)
+
+
+def workspace(name, query_symbol, dev, *sizes):
+    """A uint8 tensor on ``dev`` of the bytes that library ``name``'s ``*_workspace_bytes`` (``query_symbol``) asks for
+    ``sizes``."""
+    need = ctypes.c_uint64(0)
+    _native.check(getattr(_native.load(name), query_symbol)(*sizes, ctypes.byref(need)), name)
+    return _torch().empty(max(int(need.value), 1), dtype=_torch().uint8, device=dev)
+
+
 class Context:
     """Owns a prosstt_amd_ctx bound to ``device`` and to torch's current stream there."""
 
@@ -678,8 +699,8 @@ class _Overflow:
         if self.pairs:
             torch = _torch()
             where, values = (torch.cat([pair[i] for pair in self.pairs]) for i in (0, 1))
-            if _native.load_host().prosstt_amd_host_scatter_i32(result.data_ptr(), result.element_size(), where.data_ptr(),
-                                                               values.data_ptr(), where.numel(), HOST_THREADS) != 0:
+            if _native.load("host").prosstt_amd_host_scatter_i32(result.data_ptr(), result.element_size(), where.data_ptr(),
+                                                                 values.data_ptr(), where.numel(), HOST_THREADS) != 0:
                 raise RuntimeError("the host library refused its arguments")
 
 
@@ -698,7 +719,7 @@ def _host_lib():
     """libprosstt_amd_host.so, or _NoHostWidening (and, the first time in the process, a RuntimeWarning)."""
     global _warned_no_host_lib
     try:
-        return _native.load_host()
+        return _native.load("host")
     except RuntimeError as exc:
         if not _warned_no_host_lib:
             _warned_no_host_lib = True
@@ -939,14 +960,12 @@ class CountMatrix:
 
     def stream(self):
         """torch's current stream on the matrix's device, as the C ABI takes it."""
-        return ctypes.c_void_p(_torch().cuda.current_stream(self.device).cuda_stream)
+        return current_stream(self.device)
 
-    def workspace(self, query, check, *sizes):
-        """A uint8 device tensor of the bytes that a library's ``*_workspace_bytes`` (``query``; ``check``: its
-        _native.check_*) asks for this matrix and ``sizes``."""
-        need = ctypes.c_uint64(0)
-        check(query(self.N, self.G, *sizes, ctypes.byref(need)))
-        return _torch().empty(max(int(need.value), 1), dtype=_torch().uint8, device=self.device)
+    def workspace(self, name, query_symbol, *sizes):
+        """A uint8 device tensor of the bytes that library ``name``'s ``*_workspace_bytes`` (``query_symbol``) asks for
+        this matrix and ``sizes``."""
+        return workspace(name, query_symbol, self.device, self.N, self.G, *sizes)
 
 
 _contexts = {}

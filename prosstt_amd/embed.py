@@ -110,7 +110,7 @@ class LogNormalized:
         N, cell_of_row = m.N, m.cell_of_row
         inv = _inverse_sizes(size_factors, N)
         self.matrix = m.on_device()
-        _native.load_embed()
+        _native.load("embed")
         X = m.X
         self.counts, self.ld, self.device, self.dtype = X, m.ld, X.device, torch.float32
         self._row_of_cell = self._cell_of_row = None
@@ -126,7 +126,7 @@ class LogNormalized:
         return tuple(self.counts.shape)
 
     def _workspace(self, l):
-        return self.matrix.workspace(_native.load_embed().prosstt_amd_embed_workspace_bytes, _native.check_embed, l)
+        return self.matrix.workspace("embed", "prosstt_amd_embed_workspace_bytes", l)
 
     def _check_status(self):
         if int(self.status.item()):
@@ -155,9 +155,9 @@ class LogNormalized:
         with torch.cuda.device(self.device):
             ws = self._workspace(1)
             S = torch.empty(2, G, dtype=torch.float64, device=self.device)
-            _native.check_embed(_native.load_embed().prosstt_amd_embed_gene_moments(
+            _native.check(_native.load("embed").prosstt_amd_embed_gene_moments(
                 self.matrix.stream(), p(self.counts), N, G, self.ld, p(self.inv_size), p(ws), ws.numel(), p(S[0]),
-                p(S[1]), p(self.status)))
+                p(S[1]), p(self.status)), "embed")
             self._check_status()
             S = S.cpu().numpy()
         return S[0].copy(), S[1].copy()
@@ -171,9 +171,9 @@ class LogNormalized:
         with torch.cuda.device(self.device):
             ws = self._workspace(l)
             Y = torch.empty(N, l, dtype=torch.float32, device=self.device)
-            _native.check_embed(_native.load_embed().prosstt_amd_embed_matmul(
+            _native.check(_native.load("embed").prosstt_amd_embed_matmul(
                 self.matrix.stream(), p(self.counts), N, G, self.ld, p(self.inv_size), p(W), l, p(Y), p(ws),
-                ws.numel(), p(self.status)))
+                ws.numel(), p(self.status)), "embed")
             self._check_status()
             if self._row_of_cell is not None:
                 Y = Y.index_select(0, self._row_of_cell)
@@ -190,9 +190,9 @@ class LogNormalized:
                 Q = Q.index_select(0, self._cell_of_row)
             ws = self._workspace(l)
             Z = torch.empty(G, l, dtype=torch.float32, device=self.device)
-            _native.check_embed(_native.load_embed().prosstt_amd_embed_rmatmul(
+            _native.check(_native.load("embed").prosstt_amd_embed_rmatmul(
                 self.matrix.stream(), p(self.counts), N, G, self.ld, p(self.inv_size), p(Q), l, p(Z), p(ws),
-                ws.numel(), p(self.status)))
+                ws.numel(), p(self.status)), "embed")
             self._check_status()
         return Z
 

@@ -45,12 +45,11 @@ the host, and the run stops when the residual estimate |beta_m s_mi| of each of 
 magnitude is below ``tol``.  A disconnected graph has a repeated eigenvalue 1; a single-vector Lanczos run, like scanpy's
 ARPACK call, may not return every copy.
 """
-import ctypes
 from typing import Any, NamedTuple
 
 import numpy as np
 
-from . import _native
+from . import _native, device
 from .device import _ptr, _torch
 from .neighbors import MAX_NEIGHBORS
 
@@ -191,18 +190,6 @@ def _check_diffmap(N, n_comps, tol, seed, max_steps, out):
     return int(n_comps), limit
 
 
-def _need_device():
-    torch = _torch()
-    L = _native.load_graph()
-    if not torch.cuda.is_available():
-        raise RuntimeError("prosstt_amd needs an AMD MI355X (gfx950) device: there is no CPU fallback")
-    return L
-
-
-def _stream(dev):
-    return ctypes.c_void_p(_torch().cuda.current_stream(dev).cuda_stream)
-
-
 def _on_device(arr, dev=None):
     torch = _torch()
     if isinstance(arr, np.ndarray):
@@ -230,18 +217,16 @@ def _connectivities(L, idx, d2, N, k):
     """Connectivities of device tensors from contiguous device ``idx`` (N, k) int32 and ``d2`` float32."""
     torch = _torch()
     dev = idx.device
-    st = _stream(dev)
+    st = device.current_stream(dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     a = torch.empty((N, k), dtype=torch.float64, device=dev)
     rho = torch.empty(N, dtype=torch.float64, device=dev)
     sigma = torch.empty(N, dtype=torch.float64, device=dev)
-    _native.check_graph(L.prosstt_amd_graph_memberships(st, _ptr(idx), _ptr(d2), N, k, _ptr(a), _ptr(rho), _ptr(sigma),
-                                                        _ptr(status)))
+    _native.check(L.prosstt_amd_graph_memberships(st, _ptr(idx), _ptr(d2), N, k, _ptr(a), _ptr(rho), _ptr(sigma),
+                                                  _ptr(status)), "graph")
     _raise_status(status)
-    need = ctypes.c_uint64(0)
-    _native.check_graph(L.prosstt_amd_graph_workspace_bytes(N, k, ctypes.byref(need)))
-    ws = torch.empty(int(need.value), dtype=torch.uint8, device=dev)
-    _native.check_graph(L.prosstt_amd_graph_symmetrize_emit(st, _ptr(idx), _ptr(a), N, k, _ptr(ws), ws.numel()))
+    ws = device.workspace("graph", "prosstt_amd_graph_workspace_bytes", dev, N, k)
+    _native.check(L.prosstt_amd_graph_symmetrize_emit(st, _ptr(idx), _ptr(a), N, k, _ptr(ws), ws.numel()), "graph")
     M = 2 * N * k
     keys = ws[:8 * M].view(torch.int64)
     sorted_keys, perm = torch.sort(keys, stable=True)
@@ -252,8 +237,8 @@ def _connectivities(L, idx, d2, N, k):
     indptr = torch.empty(N + 1, dtype=torch.int64, device=dev)
     indices = torch.empty(nnz, dtype=torch.int32, device=dev)
     data = torch.empty(nnz, dtype=torch.float64, device=dev)
-    _native.check_graph(L.prosstt_amd_graph_symmetrize_fold(st, _ptr(sorted_keys), _ptr(perm), _ptr(pos), N, k, nnz, _ptr(ws),
-                                                            ws.numel(), _ptr(indptr), _ptr(indices), _ptr(data)))
+    _native.check(L.prosstt_amd_graph_symmetrize_fold(st, _ptr(sorted_keys), _ptr(perm), _ptr(pos), N, k, nnz, _ptr(ws),
+                                                      ws.numel(), _ptr(indptr), _ptr(indices), _ptr(data)), "graph")
     return Connectivities(indptr, indices, data, rho, sigma)
 
 
@@ -271,7 +256,7 @@ def connectivities(nb, *, out="scipy"):
     if out not in ("scipy", "torch"):
         raise ValueError("out must be 'scipy' or 'torch'")
     idx, d2, N, k = _check_neighbors(nb)
-    L = _need_device()
+    L = device.need_device("graph")
     torch = _torch()
     idx = _on_device(idx)
     d2 = _on_device(d2, idx.device)
@@ -319,8 +304,8 @@ def _transitions(L, g):
     T = torch.empty(nnz, dtype=torch.float64, device=dev)
     q = torch.empty(N, dtype=torch.float64, device=dev)
     z = torch.empty(N, dtype=torch.float64, device=dev)
-    _native.check_graph(L.prosstt_amd_graph_normalize(_stream(dev), _ptr(g.indptr), _ptr(g.indices), _ptr(g.data), N, nnz,
-                                                      _ptr(T), _ptr(q), _ptr(z), _ptr(status)))
+    _native.check(L.prosstt_amd_graph_normalize(device.current_stream(dev), _ptr(g.indptr), _ptr(g.indices), _ptr(g.data), N,
+                                                nnz, _ptr(T), _ptr(q), _ptr(z), _ptr(status)), "graph")
     _raise_status(status)
     return Transitions(g.indptr, g.indices, T, q, z)
 
@@ -329,7 +314,7 @@ def transitions(graph):
     """The density-normalised transition matrix T of a ``Neighbors`` or a ``Connectivities`` (the module docstring's
     operator), as a ``Transitions`` of device tensors."""
     _host_checks(graph)
-    L = _need_device()
+    L = device.need_device("graph")
     g = _as_connectivities(L, graph)
     with _torch().cuda.device(g.indptr.device):
         return _transitions(L, g)
@@ -342,15 +327,15 @@ def spmv(T, x, lanes_per_row=0):
     torch = _torch()
     if lanes_per_row not in LANES:
         raise ValueError("lanes_per_row must be 0, 4, 16 or 64 (got %r)" % (lanes_per_row,))
-    L = _need_device()
+    L = device.need_device("graph")
     N = T.indptr.numel() - 1
     if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or tuple(x.shape) != (N,) or x.device != T.data.device:
         raise ValueError("x must be a float64 vector of %d entries on %s" % (N, T.data.device))
     x = x.contiguous()
     y = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        _native.check_graph(L.prosstt_amd_graph_spmv(_stream(x.device), _ptr(T.indptr), _ptr(T.indices), _ptr(T.data), N,
-                                                     T.indices.numel(), _ptr(x), _ptr(y), lanes_per_row))
+        _native.check(L.prosstt_amd_graph_spmv(device.current_stream(x.device), _ptr(T.indptr), _ptr(T.indices), _ptr(T.data),
+                                               N, T.indices.numel(), _ptr(x), _ptr(y), lanes_per_row), "graph")
     return y
 
 
@@ -371,7 +356,7 @@ def _lanczos(L, T, n_comps, tol, seed, limit):
     torch = _torch()
     dev = T.data.device
     N, nnz = T.indptr.numel() - 1, T.indices.numel()
-    st = _stream(dev)
+    st = device.current_stream(dev)
     start = np.random.default_rng(seed).standard_normal(N)
     start /= np.linalg.norm(start)
     rows = min(limit, 4 * CHECK_EVERY) + 1
@@ -385,8 +370,8 @@ def _lanczos(L, T, n_comps, tol, seed, limit):
     for j in range(limit):
         if j + 1 >= V.shape[0]:
             V = torch.cat([V, torch.empty((min(V.shape[0], limit + 1 - V.shape[0]), N), dtype=torch.float64, device=dev)])
-        _native.check_graph(L.prosstt_amd_graph_spmv(st, _ptr(T.indptr), _ptr(T.indices), _ptr(T.data), N, nnz, _ptr(V[j]),
-                                                     _ptr(w), 0))
+        _native.check(L.prosstt_amd_graph_spmv(st, _ptr(T.indptr), _ptr(T.indices), _ptr(T.data), N, nnz, _ptr(V[j]),
+                                               _ptr(w), 0), "graph")
         alpha[j].copy_(torch.dot(w, V[j]))
         basis = V[:j + 1]
         for _ in range(2):
@@ -439,7 +424,7 @@ def diffmap(graph, n_comps=15, *, tol=1e-10, seed=0, max_steps=None, out="numpy"
     every estimate is below ``tol``."""
     N = _host_checks(graph)
     n_comps, limit = _check_diffmap(N, n_comps, tol, seed, max_steps, out)
-    L = _need_device()
+    L = device.need_device("graph")
     torch = _torch()
     g = _as_connectivities(L, graph)
     with torch.cuda.device(g.indptr.device):

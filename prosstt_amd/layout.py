@@ -48,12 +48,11 @@ reads the positions of the previous one and writes new ones, so equal inputs giv
   the other two.  ``init="random"``: default_rng(seed).uniform(-10, 10, (N, c)), cast to binary32.  Or an (N, c) array or
   device tensor of finite numbers.
 """
-import ctypes
 from typing import Any, NamedTuple
 
 import numpy as np
 
-from . import _native, graph
+from . import _native, device, graph
 from .device import _ptr, _torch
 
 LANES = graph.LANES
@@ -136,14 +135,6 @@ def _check_positions(Y, N, c, what):
     return Y
 
 
-def _need_device():
-    torch = _torch()
-    L = _native.load_layout()
-    if not torch.cuda.is_available():
-        raise RuntimeError("prosstt_amd needs an AMD MI355X (gfx950) device: there is no CPU fallback")
-    return L
-
-
 # ------------------------------------------------------------------------------------------------------------ epochs
 
 def _weights(g):
@@ -160,10 +151,10 @@ def _weights(g):
 def _epochs(L, g, p, y0, y1, epoch_begin, epoch_end, n_epochs, a, b, gamma, alpha, rate, seed, lanes_per_row):
     """Enqueue the epochs on the current stream; the tensor of (y0, y1) that holds the result."""
     N, c = y0.shape
-    _native.check_layout(L.prosstt_amd_layout_epochs(
-        graph._stream(y0.device), _ptr(g.indptr), _ptr(g.indices), _ptr(p), N, g.indices.numel(), c, _ptr(y0), _ptr(y1),
+    _native.check(L.prosstt_amd_layout_epochs(
+        device.current_stream(y0.device), _ptr(g.indptr), _ptr(g.indices), _ptr(p), N, g.indices.numel(), c, _ptr(y0), _ptr(y1),
         int(epoch_begin), int(epoch_end), int(n_epochs), float(a), float(b), float(gamma), float(alpha), int(rate), int(seed),
-        int(lanes_per_row)))
+        int(lanes_per_row)), "layout")
     return y1 if (epoch_end - epoch_begin) & 1 else y0
 
 
@@ -171,12 +162,12 @@ def _negatives(seed, epoch, e_begin, count, rate, N):
     """k of the definition's hash for entries e_begin .. e_begin + count - 1 and s = 0 .. rate - 1: a (count, rate) int32
     device tensor.  The probe the tests compare with the model bit for bit."""
     torch = _torch()
-    L = _need_device()
+    L = device.need_device("layout")
     out = torch.empty((int(count), int(rate)), dtype=torch.int32, device="cuda")
     if out.numel() == 0:
         return out
-    _native.check_layout(L.prosstt_amd_layout_negatives(graph._stream(out.device), int(seed), int(epoch), int(e_begin),
-                                                        int(count), int(rate), int(N), _ptr(out)))
+    _native.check(L.prosstt_amd_layout_negatives(device.current_stream(out.device), int(seed), int(epoch), int(e_begin),
+                                                 int(count), int(rate), int(N), _ptr(out)), "layout")
     return out
 
 
@@ -200,9 +191,9 @@ def optimize(conn, Y, epoch_begin, epoch_end, *, n_epochs, a, b, gamma=1.0, alph
     if not 0 <= epoch_begin <= epoch_end <= n_epochs:
         raise ValueError("need 0 <= epoch_begin <= epoch_end <= n_epochs (got %r, %r, %r)" % (epoch_begin, epoch_end, n_epochs))
     Y = _check_positions(Y, N, shape[1], "Y")
-    L = _need_device()
+    L = device.need_device("layout")
     torch = _torch()
-    g = graph._as_connectivities(graph._need_device(), conn)
+    g = graph._as_connectivities(device.need_device("graph"), conn)
     with torch.cuda.device(g.indptr.device):
         p = _weights(g)
         y0 = graph._on_device(Y, g.indptr.device).to(g.indptr.device).clone()
@@ -246,7 +237,7 @@ def spectral_vectors(graph_, n_components=2, *, seed=0, out="numpy"):
         raise ValueError("seed must be an integer in [0, 2^64) (got %r)" % (seed,))
     if c + 1 >= N:
         raise ValueError("need n_components + 1 < cells = %d" % N)
-    Lg = graph._need_device()
+    Lg = device.need_device("graph")
     torch = _torch()
     g = graph._as_connectivities(Lg, graph_)
     with torch.cuda.device(g.indptr.device):
@@ -294,8 +285,8 @@ def umap(graph_, n_components=2, *, min_dist=0.5, spread=1.0, n_epochs=None, alp
         start = _check_positions(init, N, c, "init")
     if a is None:
         a, b = find_ab_params(spread, min_dist)
-    L = _need_device()
-    Lg = graph._need_device()
+    L = device.need_device("layout")
+    Lg = device.need_device("graph")
     torch = _torch()
     g = graph._as_connectivities(Lg, graph_)
     dev = g.indptr.device

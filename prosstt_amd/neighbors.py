@@ -21,12 +21,11 @@ definition: it cancels for exactly the pairs that matter.
 
 There is no CPU fallback: the search runs on the current device, on the current stream.
 """
-import ctypes
 from typing import Any, NamedTuple
 
 import numpy as np
 
-from . import _native
+from . import _native, device
 from .device import _ptr, _torch
 
 MAX_DIM = 128                   # d: the widest panel the kernels take
@@ -119,9 +118,7 @@ def _panel(points, n_neighbors, out, chunk_rows):
     if not np.all(np.abs(host) < MAX_MAGNITUDE):
         raise ValueError(NOT_FINITE)
     host = np.ascontiguousarray(host, dtype=np.float32)           # rounded once, to nearest
-    _native.load_knn()
-    if not torch.cuda.is_available():
-        raise RuntimeError("prosstt_amd needs an AMD MI355X (gfx950) device: there is no CPU fallback")
+    device.need_device("knn")
     ld = -(-d // 4) * 4                                           # rows on 16 bytes: the kernels' 16-byte load path
     wide = torch.empty((N, ld), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
     P = wide[:, :d]
@@ -148,16 +145,13 @@ def knn(points, n_neighbors=15, *, out="numpy", chunk_rows=None):
     coordinate or one with |p| >= 2^59 (below that no squared distance overflows)."""
     torch = _torch()
     P, N, d, ld, k, chunk = _panel(points, n_neighbors, out, chunk_rows)
-    L = _native.load_knn()
+    L = _native.load("knn")
     with torch.cuda.device(P.device):
-        need = ctypes.c_uint64(0)
-        _native.check_knn(L.prosstt_amd_knn_workspace_bytes(N, d, k, chunk, ctypes.byref(need)))
-        ws = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=P.device)
+        ws = device.workspace("knn", "prosstt_amd_knn_workspace_bytes", P.device, N, d, k, chunk)
         index = torch.empty((N, k), dtype=torch.int32, device=P.device)
         sqdist = torch.empty((N, k), dtype=torch.float32, device=P.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(P.device).cuda_stream)
-        _native.check_knn(L.prosstt_amd_knn_search(stream, _ptr(P), N, d, ld, k, chunk, _ptr(index), _ptr(sqdist),
-                                                   _ptr(ws), ws.numel()))
+        _native.check(L.prosstt_amd_knn_search(device.current_stream(P.device), _ptr(P), N, d, ld, k, chunk, _ptr(index),
+                                               _ptr(sqdist), _ptr(ws), ws.numel()), "knn")
         if out == "torch":
             return Neighbors(index, sqdist)
         return Neighbors(index.cpu().numpy(), sqdist.cpu().numpy())

@@ -126,14 +126,14 @@ class _Outputs:
 
     def enqueue(self, m, lo, accumulate):
         """Summarise the device matrix of view m into the gene outputs and cells [lo, lo + N) (on the current stream)."""
-        L = _native.load_stats()
+        L = _native.load("stats")
         N = m.N
-        ws = m.workspace(L.prosstt_amd_stats_workspace_bytes, _native.check_stats)
+        ws = m.workspace("stats", "prosstt_amd_stats_workspace_bytes")
         p = _device._ptr
-        _native.check_stats(L.prosstt_amd_stats_count_summary(
+        _native.check(L.prosstt_amd_stats_count_summary(
             m.stream(), p(m.X), N, m.G, m.ld, p(ws), ws.numel(),
             p(self.gene_sum), p(self.gene_sumsq), p(self.gene_zeros), p(self.cell_total[lo:lo + N]),
-            p(self.cell_zeros[lo:lo + N]), p(self.status), _native.STATS_ACCUMULATE if accumulate else 0))
+            p(self.cell_zeros[lo:lo + N]), p(self.status), _native.STATS_ACCUMULATE if accumulate else 0), "stats")
 
     def fetch(self):
         """Host copies (one synchronising copy of O(cells + genes) numbers); ValueError for a negative entry."""

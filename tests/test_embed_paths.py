@@ -129,9 +129,9 @@ def test_cases_reach_every_instantiation_where_it_can_go_wrong():
 
 
 def test_restated_geometry_is_the_library_s():
-    if not os.path.exists(_native.EMBED_LIB_PATH):
+    if not os.path.exists(_native.LIBRARIES["embed"].path):
         pytest.skip("libprosstt_amd_embed.so is not built")
-    lib = ctypes.CDLL(_native.EMBED_LIB_PATH)
+    lib = ctypes.CDLL(_native.LIBRARIES["embed"].path)
     query = lib.prosstt_amd_embed_workspace_bytes
     query.restype = ctypes.c_int
     query.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64)]

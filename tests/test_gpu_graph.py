@@ -233,31 +233,31 @@ def test_refusals_through_the_abi():
     with pytest.raises(ValueError, match="positive finite"):
         graph.transitions(g._replace(data=torch.zeros_like(g.data)))
     # sizes are refused by the library before anything is enqueued
-    L = _native.load_graph()
+    L = _native.load("graph")
     N, k = 63, 5
     need = ctypes.c_uint64(0)
-    _native.check_graph(L.prosstt_amd_graph_workspace_bytes(N, k, ctypes.byref(need)))
+    _native.check(L.prosstt_amd_graph_workspace_bytes(N, k, ctypes.byref(need)), "graph")
     assert need.value >= 2 * 16 * N * k
     ws = torch.empty(need.value, dtype=torch.uint8, device="cuda")
     a = torch.full((N, k), -7.0, dtype=torch.float64, device="cuda")
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     for n, kk in ((2, 1), (63, 1), (63, 63), (2000, 1025)):
         with pytest.raises(_native.NativeError, match="need "):
-            _native.check_graph(L.prosstt_amd_graph_workspace_bytes(n, kk, ctypes.byref(need)))
+            _native.check(L.prosstt_amd_graph_workspace_bytes(n, kk, ctypes.byref(need)), "graph")
         with pytest.raises(_native.NativeError, match="need "):
-            _native.check_graph(L.prosstt_amd_graph_symmetrize_emit(stream, _ptr(idx), _ptr(a), n, kk, _ptr(ws), ws.numel()))
+            _native.check(L.prosstt_amd_graph_symmetrize_emit(stream, _ptr(idx), _ptr(a), n, kk, _ptr(ws), ws.numel()), "graph")
     with pytest.raises(_native.NativeError, match="workspace of %d bytes" % (ws.numel() - 1)):
-        _native.check_graph(L.prosstt_amd_graph_symmetrize_emit(stream, _ptr(idx), _ptr(a), N, k, _ptr(ws), ws.numel() - 1))
+        _native.check(L.prosstt_amd_graph_symmetrize_emit(stream, _ptr(idx), _ptr(a), N, k, _ptr(ws), ws.numel() - 1), "graph")
     t = graph.transitions(g)
     x = torch.ones(N, dtype=torch.float64, device="cuda")
     y = torch.full((N,), -7.0, dtype=torch.float64, device="cuda")
     for lanes in (1, 8, 32, 128, -4):
         with pytest.raises(_native.NativeError, match="lanes_per_row"):
-            _native.check_graph(L.prosstt_amd_graph_spmv(stream, _ptr(t.indptr), _ptr(t.indices), _ptr(t.data), N,
-                                                         t.indices.numel(), _ptr(x), _ptr(y), lanes))
+            _native.check(L.prosstt_amd_graph_spmv(stream, _ptr(t.indptr), _ptr(t.indices), _ptr(t.data), N,
+                                                   t.indices.numel(), _ptr(x), _ptr(y), lanes), "graph")
     with pytest.raises(_native.NativeError, match="alias"):
-        _native.check_graph(L.prosstt_amd_graph_spmv(stream, _ptr(t.indptr), _ptr(t.indices), _ptr(t.data), N,
-                                                     t.indices.numel(), _ptr(x), _ptr(x), 0))
+        _native.check(L.prosstt_amd_graph_spmv(stream, _ptr(t.indptr), _ptr(t.indices), _ptr(t.data), N,
+                                               t.indices.numel(), _ptr(x), _ptr(x), 0), "graph")
     torch.cuda.synchronize()
     assert bool((y == -7.0).all())                                # nothing was enqueued
     with pytest.raises(ValueError, match="float64 vector"):

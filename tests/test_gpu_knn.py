@@ -145,11 +145,11 @@ def test_errors_through_the_abi():
     import torch
     from prosstt_amd import _native, neighbors
     from prosstt_amd.device import _ptr
-    L = _native.load_knn()
+    L = _native.load("knn")
     N, d, k = 100, 5, 3
     P = torch.as_tensor(knn_model.gaussian(N, d, 1)).cuda()
     need = ctypes.c_uint64(0)
-    _native.check_knn(L.prosstt_amd_knn_workspace_bytes(N, d, k, 0, ctypes.byref(need)))
+    _native.check(L.prosstt_amd_knn_workspace_bytes(N, d, k, 0, ctypes.byref(need)), "knn")
     assert need.value >= 4 * N * N
     ws = torch.empty(need.value, dtype=torch.uint8, device="cuda")
     index = torch.full((N, k), -7, dtype=torch.int32, device="cuda")
@@ -160,15 +160,15 @@ def test_errors_through_the_abi():
         return L.prosstt_amd_knn_search(stream, _ptr(P), n, dd, ld, kk, chunk, _ptr(index), _ptr(sqdist), _ptr(ws), ws_bytes)
 
     with pytest.raises(_native.NativeError, match="workspace of %d bytes, %d needed" % (need.value - 1, need.value)):
-        _native.check_knn(search(d, need.value - 1))
+        _native.check(search(d, need.value - 1), "knn")
     with pytest.raises(_native.NativeError, match="row stride 4 is below the row length 5"):
-        _native.check_knn(search(d - 1, need.value))
+        _native.check(search(d - 1, need.value), "knn")
     for bad in (dict(n=1), dict(dd=0), dict(dd=129), dict(kk=0), dict(kk=N), dict(chunk=-1), dict(chunk=N + 1)):
         with pytest.raises(_native.NativeError, match="need "):
-            _native.check_knn(search(d, need.value, **bad))
+            _native.check(search(d, need.value, **bad), "knn")
     torch.cuda.synchronize()
     assert bool((index == -7).all()) and bool((sqdist == -7.0).all())        # nothing was enqueued
-    _native.check_knn(search(d, need.value))
+    _native.check(search(d, need.value), "knn")
     want_idx, want_d2 = knn_model.model(P.cpu().numpy(), k)
     np.testing.assert_array_equal(index.cpu().numpy(), want_idx)
     np.testing.assert_array_equal(sqdist.cpu().numpy(), want_d2)

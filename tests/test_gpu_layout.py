@@ -263,7 +263,7 @@ def test_refusals_through_the_abi():
         with pytest.raises(ValueError, match="not those of a CSR matrix"):
             layout.umap(conn._replace(**{field: bad}), init="random")
     # everything else is refused by the library before anything is enqueued
-    L = _native.load_layout()
+    L = _native.load("layout")
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     p = conn.data / conn.data.max()
     y1 = torch.full((N, 2), -7.0, dtype=torch.float32, device="cuda")
@@ -285,15 +285,15 @@ def test_refusals_through_the_abi():
     refusals += [(dict(lanes=lanes), "lanes_per_row") for lanes in (1, 8, 32, 128, -4)]
     for kw, text in refusals:
         with pytest.raises(_native.NativeError, match=text):
-            _native.check_layout(epochs(**kw))
+            _native.check(epochs(**kw), "layout")
     out = torch.full((4, 31), -7, dtype=torch.int32, device="cuda")
     for args, text in (((0, 4096, 0, 4, 31, 65), "epoch"), ((0, -1, 0, 4, 31, 65), "epoch"), ((0, 0, 0, 4, 32, 65), "rate"),
                        ((0, 0, 0, 4, -1, 65), "rate"), ((0, 0, 0, 4, 31, 2), "N < 2"), ((0, 0, 0, 4, 31, 1 << 31), "N < 2"),
                        ((0, 0, -1, 4, 31, 65), "e_begin"), ((0, 0, 0, -1, 31, 65), "count")):
         with pytest.raises(_native.NativeError, match=text):
-            _native.check_layout(L.prosstt_amd_layout_negatives(stream, *args, _ptr(out)))
+            _native.check(L.prosstt_amd_layout_negatives(stream, *args, _ptr(out)), "layout")
     torch.cuda.synchronize()
     assert bool((y1 == -7.0).all()) and bool((out == -7).all()) and torch.equal(Y, before)      # nothing was enqueued
-    _native.check_layout(epochs())                                # and the same call with good arguments runs
+    _native.check(epochs(), "layout")                                # and the same call with good arguments runs
     torch.cuda.synchronize()
     assert bool((y1 != -7.0).all()) and torch.equal(Y, before)

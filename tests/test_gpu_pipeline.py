@@ -310,9 +310,13 @@ def test_dense_host_returns_over_each_wire_equal_the_device_widened_ones(monkeyp
         assert got.dtype == dtype and got.flags.writeable and np.array_equal(got[order], small.cpu().numpy())
         assert not torch.from_numpy(got).is_pinned()
 
-    def no_host_library():
-        raise RuntimeError("libprosstt_amd_host.so not found")
-    monkeypatch.setattr(device._native, "load_host", no_host_library)
+    real_load = device._native.load
+
+    def no_host_library(name="sampler"):
+        if name == "host":
+            raise RuntimeError("libprosstt_amd_host.so not found")
+        return real_load(name)
+    monkeypatch.setattr(device._native, "load", no_host_library)
     monkeypatch.setattr(device, "_warned_no_host_lib", False)
     with pytest.warns(RuntimeWarning):
         for dtype, own in ((np.int64, "i64"), (np.int32, "i32")):
@@ -344,8 +348,12 @@ def test_sparse_return_over_each_wire_configuration(monkeypatch):
     real = device._csr_attempt
     monkeypatch.setattr(device, "_csr_attempt", lambda *a: (calls.append(a[6:]), real(*a))[1])
 
-    def no_host_library():
-        raise RuntimeError("libprosstt_amd_host.so not found")
+    real_load = device._native.load
+
+    def no_host_library(name="sampler"):
+        if name == "host":
+            raise RuntimeError("libprosstt_amd_host.so not found")
+        return real_load(name)
     for name, counts in (("small", small), ("large", large)):
         want = counts.cpu().numpy()
         assert np.count_nonzero(want) >= 1 << 22
@@ -356,7 +364,7 @@ def test_sparse_return_over_each_wire_configuration(monkeypatch):
             with monkeypatch.context() as m:
                 m.setattr(device, "WIDEN_ON", "device" if case == "device" else "host")
                 if case == "no host library":
-                    m.setattr(device._native, "load_host", no_host_library)
+                    m.setattr(device._native, "load", no_host_library)
                     m.setattr(device, "_warned_no_host_lib", False)
                 with pytest.warns(RuntimeWarning) if case == "no host library" else contextlib.nullcontext():
                     for chunk_bytes, row_order in ((256 << 20, None), (4 * g * 1000, None), (4 * g * 333, None),

@@ -1,20 +1,13 @@
-"""prosstt_amd.graph without a device: the header, the loader's table and the built library name the same symbols; the
-argument checks that refuse before any device use; the binary64 model (tests/graph_model.py) against its own definitions
-on the (300, 5, 5) test cloud."""
-import ctypes
-import os
-import re
-
+"""prosstt_amd.graph without a device: the argument checks that refuse before any device use; the binary64 model
+(tests/graph_model.py) against its own definitions on the (300, 5, 5) test cloud."""
 import numpy as np
 import pytest
-
-from conftest import ROOT
 
 torch = pytest.importorskip("torch")
 pytest.importorskip("scipy")
 
 import graph_model  # noqa: E402
-from prosstt_amd import _native, graph, neighbors  # noqa: E402
+from prosstt_amd import graph, neighbors  # noqa: E402
 
 N, D, K = 300, 5, 5
 
@@ -22,18 +15,6 @@ N, D, K = 300, 5, 5
 @pytest.fixture(scope="module")
 def cloud():
     return graph_model.case(N, K, D)
-
-
-def test_library_exports_every_declared_symbol():
-    header = open(os.path.join(ROOT, "include", "prosstt_amd_graph.h")).read()
-    declared = set(re.findall(r"\b(prosstt_amd_graph_[a-z_0-9]+)\s*\(", header))
-    assert declared == set(_native.GRAPH_SYMBOLS)
-    assert len(declared) == 7
-    assert _native.LIBRARIES["graph"].path == _native.GRAPH_LIB_PATH
-    if os.path.exists(_native.GRAPH_LIB_PATH):
-        lib = ctypes.CDLL(_native.GRAPH_LIB_PATH)
-        for name in declared:
-            assert hasattr(lib, name), name
 
 
 def _nb(n=20, k=3):

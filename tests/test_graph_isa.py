@@ -1,47 +1,20 @@
 """Properties of the graph kernels' gfx950 code object (prosstt_amd/csrc/graph/graph.hip), read from the ISA hipcc writes
 with the library's own flags (cross-compiles without a GPU): no floating-point atomic anywhere, and no kernel uses
 scratch."""
-import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import isa
+
 KERNELS = ["graph_memberships_kernel", "graph_emit_kernel", "graph_fold_kernel", "graph_normalize_kernelILi0E",
            "graph_normalize_kernelILi1E", "graph_normalize_kernelILi2E", "graph_spmv_kernelILi4E",
            "graph_spmv_kernelILi16E", "graph_spmv_kernelILi64E"]
 
 
-@pytest.fixture(scope="module")
-def isa():
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    tmp = tempfile.mkdtemp(prefix="prosstt_graph_isa_")
-    try:
-        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-                               "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-fPIC", "-shared",
-                               "-fvisibility=hidden", "-save-temps", "-o", os.path.join(tmp, "lib.so"),
-                               os.path.join(ROOT, "prosstt_amd", "csrc", "graph", "graph.hip")],
-                              cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        text = open(os.path.join(tmp, "graph-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    return text
-
-
-def _meta(text, mangled_part, key):
-    for blk in re.split(r"\n  - \.agpr_count", text)[1:]:
-        if re.search(r"\.name:\s+\S*%s" % mangled_part, blk):
-            return int(re.search(r"\." + key + r":\s+(\d+)", blk).group(1))
-    raise AssertionError(mangled_part)
-
-
-def test_every_kernel_is_listed(isa):
-    names = set(re.findall(r"\.name:\s+(_Z\S*graph_\S*_kernel\S*)", isa))
+def test_every_kernel_is_listed():
+    text = isa.assembly("graph")
+    names = set(re.findall(r"\.name:\s+(_Z\S*graph_\S*_kernel\S*)", text))
     names = {n for n in names if not n.endswith(".kd")}
     assert len(names) == len(KERNELS), sorted(names)
     for kernel in KERNELS:
@@ -49,20 +22,17 @@ def test_every_kernel_is_listed(isa):
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
-def test_no_scratch(isa, kernel):
-    assert _meta(isa, kernel, "private_segment_fixed_size") == 0
-    assert _meta(isa, kernel, "vgpr_spill_count") == 0
-    assert _meta(isa, kernel, "sgpr_spill_count") == 0
+def test_no_scratch(kernel):
+    text = isa.assembly("graph")
+    assert isa.meta(text, kernel, "private_segment_fixed_size") == 0
+    assert isa.meta(text, kernel, "vgpr_spill_count") == 0
+    assert isa.meta(text, kernel, "sgpr_spill_count") == 0
 
 
-# any floating-point atomic: global / flat / buffer / LDS add, min, max, pk_add on f16, bf16, f32 or f64
-FLOAT_ATOMIC = re.compile(r"\b(global|flat|buffer|ds)_(atomic_)?(add|sub|pk_add|min|max|fmin|fmax|cmpswap)\w*_(f16|bf16|f32|f64)\b"
-                          r"|\bds_(add|min|max)_rtn_f\d+\b|\b\w+_atomic_\w*f(32|64)\b")
-
-
-def test_no_floating_point_atomics(isa):
-    found = sorted(set(m.group(0) for m in FLOAT_ATOMIC.finditer(isa)))
+def test_no_floating_point_atomics():
+    text = isa.assembly("graph")
+    found = sorted(set(m.group(0) for m in isa.FLOAT_ATOMIC.finditer(text)))
     assert not found, found
     # the atomics there are: the integer OR into the status word, nothing in LDS
-    assert set(re.findall(r"\b(?:global|flat|buffer)_atomic_\w+", isa)) <= {"global_atomic_or"}
-    assert not re.findall(r"\bds_(?:add|sub|inc|dec|min|max|and|or|xor|cmpst|wrxchg)\w*", isa)
+    assert set(isa.global_atomics(text)) <= {"global_atomic_or"}
+    assert not isa.lds_atomics(text)

@@ -7,7 +7,6 @@ forked child of a process whose pool already runs.
 import ctypes
 import multiprocessing
 import os
-import re
 import threading
 
 import numpy as np
@@ -18,10 +17,10 @@ from conftest import ROOT
 
 def lib():
     from prosstt_amd import _native
-    if not os.path.exists(_native.HOST_LIB_PATH):
+    if not os.path.exists(_native.LIBRARIES["host"].path):
         import subprocess
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "prosstt_amd", "csrc", "host"), "all"])
-    return _native.load_host()
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "prosstt_amd", "csrc"), "host"])
+    return _native.load("host")
 
 
 def widen(L, x, threads, offset=0):
@@ -30,17 +29,6 @@ def widen(L, x, threads, offset=0):
     assert rc == 0
     assert np.all(y[:offset] == -7) and np.all(y[offset + x.size:] == -7), "wrote outside its range"
     return y[offset:offset + x.size]
-
-
-def test_header_and_library_agree():
-    from prosstt_amd import _native
-    L = lib()
-    text = open(os.path.join(ROOT, "include", "prosstt_amd_host.h")).read()
-    declared = sorted(set(re.findall(r"\b(prosstt_amd_host_\w+)\s*\(", text)))
-    assert declared == sorted(_native.HOST_SYMBOLS)
-    for name in declared:
-        assert getattr(L, name) is not None
-    assert L.prosstt_amd_host_has_avx2() in (0, 1)
 
 
 def test_widening_equals_astype_for_every_length_alignment_and_thread_count():

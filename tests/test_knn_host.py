@@ -1,19 +1,13 @@
 """neighbors.knn without a device: the scalar model (tests/knn_model.py) against a binary64 brute force and on exact ties;
-the argument checks that refuse before any device use; the header, the loader's table and the built library name the
-same symbols; Neighbors.distances and to_csr() on a hand-made result."""
-import ctypes
-import os
-import re
-
+the argument checks that refuse before any device use; Neighbors.distances and to_csr() on a hand-made result."""
 import numpy as np
 import pytest
 
-from conftest import ROOT
 import knn_model
 
 torch = pytest.importorskip("torch")
 
-from prosstt_amd import _native, neighbors  # noqa: E402
+from prosstt_amd import neighbors  # noqa: E402
 
 
 def test_model_against_binary64():
@@ -92,17 +86,6 @@ def test_refusals_before_any_device_use():
             neighbors.knn(Q, 3)
         with pytest.raises(ValueError, match="finite"):
             neighbors.knn(torch.as_tensor(Q), 3)                  # a CPU tensor is a host array
-
-
-def test_library_exports_every_declared_symbol():
-    header = open(os.path.join(ROOT, "include", "prosstt_amd_knn.h")).read()
-    declared = set(re.findall(r"\b(prosstt_amd_knn_[a-z_0-9]+)\s*\(", header))
-    assert declared == set(_native.KNN_SYMBOLS)
-    assert len(declared) == 3
-    if os.path.exists(_native.KNN_LIB_PATH):
-        lib = ctypes.CDLL(_native.KNN_LIB_PATH)
-        for name in declared:
-            assert hasattr(lib, name), name
 
 
 def test_neighbors_result():

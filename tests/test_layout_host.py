@@ -1,43 +1,22 @@
-"""prosstt_amd.layout without a device: the header, the loader's table and the built library name the same symbols; the
-argument checks that refuse before any device use; the fit of a and b; the binary64 model (tests/layout_model.py) against
-its own definition: the schedule, the hash, the trustworthiness score, the start's scaling and a whole run."""
-import ctypes
-import os
-import re
-
+"""prosstt_amd.layout without a device: the argument checks that refuse before any device use; the fit of a and b; the
+binary64 model (tests/layout_model.py) against its own definition: the schedule, the hash, the trustworthiness score, the start's scaling and a whole run."""
 import numpy as np
 import pytest
-
-from conftest import ROOT
 
 torch = pytest.importorskip("torch")
 pytest.importorskip("scipy")
 
 import graph_model  # noqa: E402
 import layout_model  # noqa: E402
-from prosstt_amd import _native, graph, layout, neighbors  # noqa: E402
-
-
-def test_library_exports_every_declared_symbol():
-    header = open(os.path.join(ROOT, "include", "prosstt_amd_layout.h")).read()
-    declared = set(re.findall(r"\b(prosstt_amd_layout_[a-z_0-9]+)\s*\(", header))
-    assert declared == set(_native.LAYOUT_SYMBOLS)
-    assert len(declared) == 3
-    assert _native.LIBRARIES["layout"].path == _native.LAYOUT_LIB_PATH
-    assert list(_native.LIBRARIES)[-1] == "layout" and len(_native.LIBRARIES) == 7
-    if os.path.exists(_native.LAYOUT_LIB_PATH):
-        lib = ctypes.CDLL(_native.LAYOUT_LIB_PATH)
-        for name in declared:
-            assert hasattr(lib, name), name
+from prosstt_amd import device, graph, layout, neighbors  # noqa: E402
 
 
 @pytest.fixture
 def no_device(monkeypatch):
-    """Any step towards the device fails the test: the loaders of both libraries and torch's own switch."""
+    """Any step towards the device fails the test: the loader of every library and torch's own switch."""
     def reached(*args, **kwargs):
         raise AssertionError("the device was reached")
-    monkeypatch.setattr(layout, "_need_device", reached)
-    monkeypatch.setattr(graph, "_need_device", reached)
+    monkeypatch.setattr(device, "need_device", reached)
     monkeypatch.setattr(graph, "_on_device", reached)
 
 

@@ -425,14 +425,11 @@ def build(name):
             files[fn] = files[fn].replace(old, new)
     for fn, text in files.items():
         open(os.path.join(work, "prosstt_amd", "csrc", fn), "w").write(text)
-    lib = os.path.join(OUT, "libprosstt_amd_%s.so" % name)
-    # ABLATE_FLAGS="-mllvm -amdgpu-sched-strategy=max-memory-clause" ABLATE_SUFFIX=_maxmem: the same variant under other compiler flags
+    # ABLATE_FLAGS="-mllvm <option>" ABLATE_SUFFIX=_other: the same variant with further compiler flags, after the makefile's
     lib = os.path.join(OUT, "libprosstt_amd_%s%s.so" % (name, os.environ.get("ABLATE_SUFFIX", "")))
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-                           "-mllvm", "-amdgpu-sched-strategy=max-ilp",
-                           *os.environ.get("ABLATE_FLAGS", "").split(),
-                           "-fPIC", "-shared", "-fvisibility=hidden", "-o", lib,
-                           os.path.join(work, "prosstt_amd", "csrc", "prosstt_amd.hip")])
+    subprocess.check_call(["make", "-C", os.path.join(work, "prosstt_amd", "csrc"), "sampler", "LIBDIR=" + os.path.join(work, "lib"),
+                           "EXTRA=" + os.environ.get("ABLATE_FLAGS", "")])
+    shutil.move(os.path.join(work, "lib", "libprosstt_amd.so"), lib)
     shutil.rmtree(work, ignore_errors=True)
     return lib
 

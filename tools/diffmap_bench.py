@@ -64,7 +64,7 @@ def main():
     import graph_model
     from prosstt_amd import _native, graph, neighbors
     from prosstt_amd.device import _ptr
-    L = _native.load_graph()
+    L = _native.load("graph")
     N, d = args.cells, args.dim
     print("device: %s; cloud: tree_points(%d, %d, seed %d)" % (torch.cuda.get_device_name(0), N, d, N))
     P = torch.from_numpy(graph_model.tree_points(N, d, N)).cuda()
@@ -83,8 +83,8 @@ def main():
         floor_us = (12.0 * nnz + 8.0 * nnz + 16.0 * N) / 8e12 * 1e6
         for lanes in (4, 16, 64, 0):
             def product():
-                _native.check_graph(L.prosstt_amd_graph_spmv(stream, _ptr(t.indptr), _ptr(t.indices), _ptr(t.data), N, nnz,
-                                                             _ptr(x), _ptr(y), lanes))
+                _native.check(L.prosstt_amd_graph_spmv(stream, _ptr(t.indptr), _ptr(t.indices), _ptr(t.data), N, nnz,
+                                                       _ptr(x), _ptr(y), lanes), "graph")
             us = 1e3 * event_ms(product, args.spmv_reps)
             print("  spmv lanes %2d    %9.2f us   (%.1f GB/s of entries; the bytes at 8 TB/s: %.2f us)"
                   % (lanes, us, 12.0 * nnz / us / 1e3, floor_us))

@@ -23,10 +23,10 @@ def kernel_times(op, l, reps):
     """ms per call of each entry point, enqueued back to back without the wrapper's status check."""
     import torch
     from prosstt_amd import _native, device
-    L = _native.load_embed()
+    L = _native.load("embed")
     p = device._ptr
     N, G = op.shape
-    ws = op.matrix.workspace(L.prosstt_amd_embed_workspace_bytes, _native.check_embed, l)
+    ws = op.matrix.workspace("embed", "prosstt_amd_embed_workspace_bytes", l)
     W = torch.randn(G, l, device=op.device)
     Q = torch.randn(N, l, device=op.device)
     Y = torch.empty(N, l, device=op.device)
@@ -43,11 +43,11 @@ def kernel_times(op, l, reps):
     out = {}
     for name, call in calls.items():
         for _ in range(3):
-            _native.check_embed(call())
+            _native.check(call(), "embed")
         start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         start.record()
         for _ in range(reps):
-            _native.check_embed(call())
+            _native.check(call(), "embed")
         stop.record()
         stop.synchronize()
         out[name] = start.elapsed_time(stop) / reps

@@ -9,7 +9,7 @@ import torch
 sys.path.insert(0, ".")
 from prosstt_amd import _native  # noqa: E402
 
-L = _native.load_host()
+L = _native.load("host")
 for name in ("prosstt_amd_host_widen_u16_i64", "prosstt_amd_host_widen_u16_i32"):
     getattr(L, name).argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32]
 n = 1_000_000_000

@@ -13,7 +13,7 @@ from prosstt_amd import _native  # noqa: E402
 
 print("THP:", open("/sys/kernel/mm/transparent_hugepage/enabled").read().strip(),
       "| defrag:", open("/sys/kernel/mm/transparent_hugepage/defrag").read().strip())
-L = _native.load_host()
+L = _native.load("host")
 n = 1_000_000_000
 src = torch.ones(n, dtype=torch.int16, pin_memory=torch.cuda.is_available())
 

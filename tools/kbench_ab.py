@@ -30,7 +30,7 @@ vp, i32, i64, u32, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes
 class Variant:
     def __init__(self, path):
         self.name = os.path.basename(path)
-        self.lib = ctypes.CDLL(_native.LIB_PATH if path == "shipped" else os.path.abspath(path))
+        self.lib = ctypes.CDLL(_native.LIBRARIES["sampler"].path if path == "shipped" else os.path.abspath(path))
         self.lib.prosstt_amd_ctx_create.argtypes = [ctypes.c_int, vp, ctypes.POINTER(vp)]
         self.lib.prosstt_amd_sample_counts.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, i64, u64, u64, vp, vp, i64, u32]
         self.lib.prosstt_amd_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]

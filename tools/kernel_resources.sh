@@ -1,12 +1,11 @@
 #!/bin/bash
-# Register / LDS use of every kernel of the library, from the code object's own metadata (hipcc -save-temps).
+# Register / LDS use of every kernel of the library, from the code object's own metadata (the makefile's isa-sampler).
 # usage: tools/kernel_resources.sh > profiles/rNN_kernel_resources.txt
 R="$(cd "$(dirname "$0")/.." && pwd)"; T=$(mktemp -d); cd $T
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-sched-strategy=max-ilp -fPIC -shared -fvisibility=hidden -save-temps \
-    -o $T/lib.so $R/prosstt_amd/csrc/prosstt_amd.hip > /dev/null 2>&1
+make -C $R/prosstt_amd/csrc isa-sampler ISA_DIR=$T > /dev/null 2>&1
 python3 - <<PY
 import re, subprocess
-txt = open("$T/prosstt_amd-hip-amdgcn-amd-amdhsa-gfx950.s").read()
+txt = open("$T/sampler.s").read()
 print("# kernel_source_sha: %s   (fields of the .amdgpu_metadata note of the gfx950 code object)" % subprocess.check_output(
     ["python3", "-c", "import sys; sys.path.insert(0, '$R'); import bench; print(bench.kernel_source_sha())"]).decode().strip())
 for blk in re.split(r"\n  - \.agpr_count", txt)[1:]:

@@ -40,19 +40,19 @@ def library_ms(P, k, chunk, reps):
     """(ms per bare C call, warm; indices; rows per chunk) of the search over the f32 device panel P."""
     import torch
     from prosstt_amd import _native, device
-    L = _native.load_knn()
+    L = _native.load("knn")
     p = device._ptr
     N, d = P.shape
     need = ctypes.c_uint64(0)
-    _native.check_knn(L.prosstt_amd_knn_workspace_bytes(N, d, k, chunk, ctypes.byref(need)))
+    _native.check(L.prosstt_amd_knn_workspace_bytes(N, d, k, chunk, ctypes.byref(need)), "knn")
     ws = torch.empty(need.value, dtype=torch.uint8, device=P.device)
     index = torch.empty((N, k), dtype=torch.int32, device=P.device)
     sqdist = torch.empty((N, k), dtype=torch.float32, device=P.device)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def call():
-        _native.check_knn(L.prosstt_amd_knn_search(st, p(P), N, d, P.stride(0), k, chunk, p(index), p(sqdist), p(ws),
-                                                   ws.numel()))
+        _native.check(L.prosstt_amd_knn_search(st, p(P), N, d, P.stride(0), k, chunk, p(index), p(sqdist), p(ws),
+                                               ws.numel()), "knn")
     call()
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     start.record()

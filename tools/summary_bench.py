@@ -21,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 def kernel_time(X, reps):
     import torch
     from prosstt_amd import _native, device
-    L = _native.load_stats()
+    L = _native.load("stats")
     p = device._ptr
     m = device.CountMatrix(X, "summary_bench").on_device()
     genes = torch.zeros(4, m.G, dtype=torch.int64, device=m.device)          # sum, sumsq (low, high), zeros
@@ -29,10 +29,10 @@ def kernel_time(X, reps):
     status = torch.zeros(1, dtype=torch.int32, device=m.device)
 
     def enqueue():                                       # what summary.count_summary enqueues, workspace included
-        ws = m.workspace(L.prosstt_amd_stats_workspace_bytes, _native.check_stats)
-        _native.check_stats(L.prosstt_amd_stats_count_summary(
+        ws = m.workspace("stats", "prosstt_amd_stats_workspace_bytes")
+        _native.check(L.prosstt_amd_stats_count_summary(
             m.stream(), p(m.X), m.N, m.G, m.ld, p(ws), ws.numel(), p(genes[0]), p(genes[1:3]), p(genes[3]), p(cells[0]),
-            p(cells[1]), p(status), 0))
+            p(cells[1]), p(status), 0), "stats")
 
     for _ in range(3):
         enqueue()

@@ -63,7 +63,7 @@ def main():
     import layout_model
     from prosstt_amd import _native, graph, layout, neighbors
     from prosstt_amd.device import _ptr
-    L = _native.load_layout()
+    L = _native.load("layout")
     N, d, E, k = args.cells, args.dim, args.epochs, 14
     print("device: %s; cloud: tree_points(%d, %d, seed %d), k = %d" % (torch.cuda.get_device_name(0), N, d, N, k))
     points = graph_model.tree_points(N, d, N)
@@ -103,9 +103,9 @@ def main():
             y0.copy_(first)
             begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             begin.record()
-            _native.check_layout(L.prosstt_amd_layout_epochs(stream, _ptr(conn.indptr), _ptr(conn.indices), _ptr(weights), n,
-                                                             conn.indices.numel(), 2, _ptr(y0), _ptr(y1), 0, E, E, a, b, 1.0, 1.0,
-                                                             rate, 0, lanes))
+            _native.check(L.prosstt_amd_layout_epochs(stream, _ptr(conn.indptr), _ptr(conn.indices), _ptr(weights), n,
+                                                      conn.indices.numel(), 2, _ptr(y0), _ptr(y1), 0, E, E, a, b, 1.0, 1.0,
+                                                      rate, 0, lanes), "layout")
             end.record()
             end.synchronize()
             if rep:
