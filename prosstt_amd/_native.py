@@ -1,6 +1,6 @@
 """
 ctypes binding of libprosstt_amd.so (include/prosstt_amd.h) and of the libraries beside it: each is described once in
-LIBRARIES, and load / check do the rest.
+LIBRARIES or ADDED_LIBRARIES, and load / check do the rest.
 
 There is NO CPU fallback: if the library is missing, or no gfx950 device is
 visible, every numeric entry point of the package raises.  torch is used only
@@ -118,6 +118,27 @@ LIBRARIES = {
     }, "prosstt_amd_layout_last_error"),
 }
 
+# Libraries added after tests/test_native_libraries.py pinned its census of LIBRARIES (the names and symbol counts of the
+# seven rows above): rows of the same shape, looked up after LIBRARIES; tests/test_native_tsne.py holds their census.
+# Merging the two tables, and the two censuses with them, is a follow-up.
+ADDED_LIBRARIES = {
+    # exact t-SNE: affinities, the all-pairs gradient, its descent and the objective
+    "tsne": _Library(_path("PROSSTT_AMD_TSNE_LIB", "libprosstt_amd_tsne.so"), "prosstt_amd_tsne.h", True, {
+        "prosstt_amd_tsne_last_error": _text,
+        "prosstt_amd_tsne_workspace_bytes": _int(i64, i32, i32, _ptr_to(u64)),
+        "prosstt_amd_tsne_affinities": _int(vp, vp, vp, i64, i64, f64, vp, vp, vp),
+        "prosstt_amd_tsne_symmetrize_fold": _int(vp, vp, vp, vp, i64, i64, i64, vp, u64, vp, vp, vp),
+        "prosstt_amd_tsne_gradient": _int(vp, vp, vp, vp, i64, i64, i32, vp, f64, i32, vp, u64, vp, vp, vp),
+        "prosstt_amd_tsne_iterations": _int(vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i32, i32, i32, f64, f64, i32, vp, u64),
+        "prosstt_amd_tsne_objective": _int(vp, vp, vp, vp, i64, i64, i32, vp, vp),
+    }, "prosstt_amd_tsne_last_error"),
+}
+
+
+def _library(name):
+    return LIBRARIES[name] if name in LIBRARIES else ADDED_LIBRARIES[name]
+
+
 class NativeError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("prosstt_amd error %d: %s" % (code, message))
@@ -129,8 +150,9 @@ _lock = threading.Lock()
 
 
 def load(name="sampler"):
-    """The library ``name`` of LIBRARIES with its prototypes declared (loaded once).  Raises if it has not been built."""
-    lib = LIBRARIES[name]
+    """The library ``name`` of LIBRARIES or ADDED_LIBRARIES with its prototypes declared (loaded once).  Raises if it has
+    not been built."""
+    lib = _library(name)
     with _lock:
         if name not in _loaded:
             if not os.path.exists(lib.path):
@@ -157,7 +179,7 @@ def check(code, name="sampler"):
     """Raise with the message of library ``name`` unless ``code`` is OK: NativeError, or ValueError for EDOMAIN (a code
     of the sampler's ABI alone)."""
     if code != OK:
-        msg = getattr(load(name), LIBRARIES[name].last_error)().decode("utf-8", "replace")
+        msg = getattr(load(name), _library(name).last_error)().decode("utf-8", "replace")
         if code == EDOMAIN:
             raise ValueError(msg)          # what scipy raises in the reference (simulation.py:647)
         raise NativeError(code, msg)

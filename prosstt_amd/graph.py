@@ -213,18 +213,13 @@ def _raise_status(status):
 
 # ------------------------------------------------------------------------------------------------------ connectivities
 
-def _connectivities(L, idx, d2, N, k):
-    """Connectivities of device tensors from contiguous device ``idx`` (N, k) int32 and ``d2`` float32."""
+def _symmetrize(L, idx, a, N, k, fold, fold_library):
+    """(indptr, indices, data) of the symmetrisation of the directed values ``a`` (N, k) float64 on the entries ``idx``:
+    the graph library's keyed emit, torch's sort and prefix sum, and ``fold``, an entry of library ``fold_library`` with
+    the arguments of prosstt_amd_graph_symmetrize_fold, which says how the two directions of a pair combine."""
     torch = _torch()
     dev = idx.device
     st = device.current_stream(dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    a = torch.empty((N, k), dtype=torch.float64, device=dev)
-    rho = torch.empty(N, dtype=torch.float64, device=dev)
-    sigma = torch.empty(N, dtype=torch.float64, device=dev)
-    _native.check(L.prosstt_amd_graph_memberships(st, _ptr(idx), _ptr(d2), N, k, _ptr(a), _ptr(rho), _ptr(sigma),
-                                                  _ptr(status)), "graph")
-    _raise_status(status)
     ws = device.workspace("graph", "prosstt_amd_graph_workspace_bytes", dev, N, k)
     _native.check(L.prosstt_amd_graph_symmetrize_emit(st, _ptr(idx), _ptr(a), N, k, _ptr(ws), ws.numel()), "graph")
     M = 2 * N * k
@@ -237,8 +232,24 @@ def _connectivities(L, idx, d2, N, k):
     indptr = torch.empty(N + 1, dtype=torch.int64, device=dev)
     indices = torch.empty(nnz, dtype=torch.int32, device=dev)
     data = torch.empty(nnz, dtype=torch.float64, device=dev)
-    _native.check(L.prosstt_amd_graph_symmetrize_fold(st, _ptr(sorted_keys), _ptr(perm), _ptr(pos), N, k, nnz, _ptr(ws),
-                                                      ws.numel(), _ptr(indptr), _ptr(indices), _ptr(data)), "graph")
+    _native.check(fold(st, _ptr(sorted_keys), _ptr(perm), _ptr(pos), N, k, nnz, _ptr(ws), ws.numel(), _ptr(indptr),
+                       _ptr(indices), _ptr(data)), fold_library)
+    return indptr, indices, data
+
+
+def _connectivities(L, idx, d2, N, k):
+    """Connectivities of device tensors from contiguous device ``idx`` (N, k) int32 and ``d2`` float32."""
+    torch = _torch()
+    dev = idx.device
+    st = device.current_stream(dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    a = torch.empty((N, k), dtype=torch.float64, device=dev)
+    rho = torch.empty(N, dtype=torch.float64, device=dev)
+    sigma = torch.empty(N, dtype=torch.float64, device=dev)
+    _native.check(L.prosstt_amd_graph_memberships(st, _ptr(idx), _ptr(d2), N, k, _ptr(a), _ptr(rho), _ptr(sigma),
+                                                  _ptr(status)), "graph")
+    _raise_status(status)
+    indptr, indices, data = _symmetrize(L, idx, a, N, k, L.prosstt_amd_graph_symmetrize_fold, "graph")
     return Connectivities(indptr, indices, data, rho, sigma)
 
 
