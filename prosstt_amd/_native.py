@@ -1,6 +1,6 @@
 """
 ctypes binding of libprosstt_amd.so (include/prosstt_amd.h) and of the libraries beside it: each is described once in
-LIBRARIES or ADDED_LIBRARIES, and load / check do the rest.
+LIBRARIES, ADDED_LIBRARIES or LATER_LIBRARIES, and load / check do the rest.
 
 There is NO CPU fallback: if the library is missing, or no gfx950 device is
 visible, every numeric entry point of the package raises.  torch is used only
@@ -134,9 +134,25 @@ ADDED_LIBRARIES = {
     }, "prosstt_amd_tsne_last_error"),
 }
 
+# Every library added after that goes HERE: tests/test_native_tsne.py pinned the names of ADDED_LIBRARIES in its turn.  Rows
+# of the same shape, looked up after the other two tables; tests/test_native_later.py checks each row against its header,
+# its makefile row and the built library, and takes the symbol count from the header, so that a new row breaks no test.
+LATER_LIBRARIES = {
+    # diffusion pseudotime: distance rows of a diffusion map and the concordance sums of its branching
+    "dpt": _Library(_path("PROSSTT_AMD_DPT_LIB", "libprosstt_amd_dpt.so"), "prosstt_amd_dpt.h", True, {
+        "prosstt_amd_dpt_last_error": _text,
+        "prosstt_amd_dpt_workspace_bytes": _int(i64, i32, i32, _ptr_to(u64)),
+        "prosstt_amd_dpt_rows": _int(vp, vp, i64, vp, i64, i64, vp, i64, vp),
+        "prosstt_amd_dpt_concordance": _int(vp, vp, vp, i64, i32, i32, vp, u64, vp, vp),
+    }, "prosstt_amd_dpt_last_error"),
+}
+
 
 def _library(name):
-    return LIBRARIES[name] if name in LIBRARIES else ADDED_LIBRARIES[name]
+    for table in (LIBRARIES, ADDED_LIBRARIES):
+        if name in table:
+            return table[name]
+    return LATER_LIBRARIES[name]
 
 
 class NativeError(RuntimeError):
@@ -150,7 +166,7 @@ _lock = threading.Lock()
 
 
 def load(name="sampler"):
-    """The library ``name`` of LIBRARIES or ADDED_LIBRARIES with its prototypes declared (loaded once).  Raises if it has
+    """The library ``name`` of LIBRARIES, ADDED_LIBRARIES or LATER_LIBRARIES with its prototypes declared (loaded once).  Raises if it has
     not been built."""
     lib = _library(name)
     with _lock:
