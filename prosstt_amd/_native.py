@@ -145,6 +145,12 @@ LATER_LIBRARIES = {
         "prosstt_amd_dpt_rows": _int(vp, vp, i64, vp, i64, i64, vp, i64, vp),
         "prosstt_amd_dpt_concordance": _int(vp, vp, vp, i64, i32, i32, vp, u64, vp, vp),
     }, "prosstt_amd_dpt_last_error"),
+    # marker genes: per-group sums over the log-normalised count matrix
+    "markers": _Library(_path("PROSSTT_AMD_MARKERS_LIB", "libprosstt_amd_markers.so"), "prosstt_amd_markers.h", True, {
+        "prosstt_amd_markers_last_error": _text,
+        "prosstt_amd_markers_workspace_bytes": _int(i64, i64, i64, i64, _ptr_to(u64)),
+        "prosstt_amd_markers_group_moments": _int(vp, vp, i64, i64, i64, vp, vp, i64, vp, i64, i64, vp, u64, vp, vp, vp, vp, vp),
+    }, "prosstt_amd_markers_last_error"),
 }
 
 

@@ -22,6 +22,7 @@
 #define ABI_EINVAL PROSSTT_AMD_EMBED_EINVAL
 #define ABI_EHIP PROSSTT_AMD_EMBED_EHIP
 #include "../abi_util.h"
+#include "../log1p_entry.h"                 // entry(): the float32 log1p(x * inv), shared with markers/markers.hip
 
 namespace {
 
@@ -30,7 +31,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kStep = 32;                   // genes (matmul) or rows (rmatmul) per step of the k loop
 constexpr int kRowsMM = 128;                // matmul: rows per block, 32 per wave
 constexpr int kGenesRM = 256;               // rmatmul: genes per block, 64 per wave
-constexpr float kLn2 = 0.693147180559945309f;
 
 struct Geometry {
     int64_t lp = 0;                                   // panel width rounded up to 32
@@ -62,18 +62,6 @@ Geometry geometry(int64_t N, int64_t G, int64_t l)
     g.bytes = g.m_bytes > g.mm_bytes ? g.m_bytes : g.mm_bytes;
     if (g.rm_bytes > g.bytes) g.bytes = g.rm_bytes;
     return g;
-}
-
-// log1p(x * inv) in f32, relative error below 2^-20 against binary64 log1p(x / s): u = fl(1 + y) and u - 1 is exact, so
-// log1p(y) = log(u) * y / (u - 1) loses only the roundings of v_log_f32, v_rcp_f32 (2^-23 each) and four products; when
-// u == 1, log1p(y) = y to within y / 2 < 2^-25.
-__device__ __forceinline__ float entry(int32_t x, float inv)
-{
-    const float y = (float)x * inv;
-    const float u = 1.0f + y;
-    const float d = u - 1.0f;
-    const float r = (__builtin_amdgcn_logf(u) * kLn2) * (y * __builtin_amdgcn_rcpf(d));
-    return d == 0.0f ? y : r;
 }
 
 __device__ __forceinline__ f32x16 mfma(float a, float b, const f32x16& c)
