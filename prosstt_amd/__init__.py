@@ -24,6 +24,11 @@ The UMAP layout of that neighbour graph on the device (what ``tl.umap`` computes
     from prosstt_amd import layout
     lay = layout.umap(nb)                             # lay.embedding (cells, 2) float32
 
+Louvain clusters of that neighbour graph on the device (what ``tl.louvain`` computes, in a reproducible form):
+
+    from prosstt_amd import cluster
+    cl = cluster.louvain(nb)                          # cl.labels (cells,) int32, 0 the largest cluster; cl.modularity
+
 or, for unmodified scripts that say ``from prosstt import ...``:
 
     import prosstt_amd; prosstt_amd.install_as_prosstt()

@@ -151,6 +151,16 @@ LATER_LIBRARIES = {
         "prosstt_amd_markers_workspace_bytes": _int(i64, i64, i64, i64, _ptr_to(u64)),
         "prosstt_amd_markers_group_moments": _int(vp, vp, i64, i64, i64, vp, vp, i64, vp, i64, i64, vp, u64, vp, vp, vp, vp, vp),
     }, "prosstt_amd_markers_last_error"),
+    # Louvain clustering of the connectivities: quantised weights, sweeps, community totals and the aggregation
+    "cluster": _Library(_path("PROSSTT_AMD_CLUSTER_LIB", "libprosstt_amd_cluster.so"), "prosstt_amd_cluster.h", True, {
+        "prosstt_amd_cluster_last_error": _text,
+        "prosstt_amd_cluster_workspace_bytes": _int(i64, i64, _ptr_to(u64)),
+        "prosstt_amd_cluster_quantize": _int(vp, vp, vp, vp, i64, i64, vp, vp, vp),
+        "prosstt_amd_cluster_sweep": _int(vp, vp, vp, vp, vp, i64, i64, vp, i64, i64, i64, vp, vp, i64, f64, i32, i32, vp, vp, vp),
+        "prosstt_amd_cluster_totals": _int(vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp),
+        "prosstt_amd_cluster_aggregate_emit": _int(vp, vp, vp, i64, i64, vp, i64, vp, u64, vp),
+        "prosstt_amd_cluster_aggregate_fold": _int(vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp),
+    }, "prosstt_amd_cluster_last_error"),
 }
 
 
