@@ -161,6 +161,12 @@ LATER_LIBRARIES = {
         "prosstt_amd_cluster_aggregate_emit": _int(vp, vp, vp, i64, i64, vp, i64, vp, u64, vp),
         "prosstt_amd_cluster_aggregate_fold": _int(vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp),
     }, "prosstt_amd_cluster_last_error"),
+    # Wilcoxon marker genes: per gene a sort of the log-normalised entries, folded into exact rank sums per group
+    "ranks": _Library(_path("PROSSTT_AMD_RANKS_LIB", "libprosstt_amd_ranks.so"), "prosstt_amd_ranks.h", True, {
+        "prosstt_amd_ranks_last_error": _text,
+        "prosstt_amd_ranks_workspace_bytes": _int(i64, i64, i64, _ptr_to(u64)),
+        "prosstt_amd_ranks_rank_sums": _int(vp, vp, i64, i64, i64, vp, vp, i64, vp, i64, i64, i64, vp, u64, vp, vp, vp),
+    }, "prosstt_amd_ranks_last_error"),
 }
 
 

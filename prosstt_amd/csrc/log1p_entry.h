@@ -1,6 +1,6 @@
 // The float32 entry A[i][j] = log1p(X[i][j] * inv_size[i]) of the log-normalised count matrix, formed in registers: one
 // definition for every library that reads the matrix this way, so that their entries are equal to the bit.
-// Internal: included by embed/embed.hip and markers/markers.hip, and not installed under include/.
+// Internal: included by embed/embed.hip, markers/markers.hip and ranks/ranks.hip, and not installed under include/.
 #pragma once
 
 #include <hip/hip_runtime.h>

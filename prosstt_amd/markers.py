@@ -27,6 +27,9 @@ are the totals over every group minus group 1's, n2 = n_total - n1):
     logfoldchanges = log2((expm1(m1) + 1e-9) / (expm1(m2) + 1e-9));  pts = nz1 / n1, pts_rest = nz2 / n2
 
 Every group keeps its row (with a reference group, that group's own row compares it with itself: t = 0).
+
+``method="wilcoxon"`` (``RANK_METHODS``) ranks by the Wilcoxon rank-sum z instead.  It cannot be computed from these sums: it
+needs every gene's entries ranked, which ``prosstt_amd.ranks`` does on the device; ``rank_genes_groups`` runs both.
 """
 from typing import Any, NamedTuple
 
@@ -39,6 +42,7 @@ from .layout import _number
 
 MAX_GROUPS = 1024               # PROSSTT_AMD_MARKERS_MAX_GROUPS
 METHODS = ("t-test", "t-test_overestim_var")
+RANK_METHODS = ("wilcoxon",)    # ranked from the matrix itself, not from a GroupMoments: prosstt_amd/ranks.py
 NEGATIVE, ROW_RANGE, GROUP_RANGE = 1, 2, 4       # the bits of the pass's status word
 
 
@@ -167,6 +171,21 @@ def _rows_per_block(v):
     return int(v)
 
 
+def _row_list(codes, K, cell_of_row, dev):
+    """(n, rows, start): the cells per group (host int64), and on ``dev`` the rows of the labelled cells sorted by group (int32,
+    in the matrix's order within a group) with the K + 1 offsets of the groups in it (int64).  torch's sort, ``bincount`` and
+    ``cumsum`` on the current stream."""
+    torch = _torch()
+    keep = codes >= 0
+    n = np.bincount(codes[keep], minlength=K).astype(np.int64)
+    n_sel = int(n.sum())
+    key = torch.as_tensor(codes_in_row_order(np.where(keep, codes, K), cell_of_row)).to(dev)   # left out: last
+    rows = torch.sort(key, stable=True).indices[:n_sel].to(torch.int32)
+    start = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    start[1:] = torch.cumsum(torch.bincount(key, minlength=K + 1)[:K], 0)
+    return n, rows, start
+
+
 def group_moments(counts, size_factors, labels, *, rows_per_block=0, out="numpy"):
     """``GroupMoments`` of an int32 device count matrix for one label per cell.
 
@@ -188,15 +207,10 @@ def group_moments(counts, size_factors, labels, *, rows_per_block=0, out="numpy"
     torch = _torch()
     N, G = op.shape
     K = len(groups)
-    keep = codes >= 0
-    n = np.bincount(codes[keep], minlength=K).astype(np.int64)
-    n_sel = int(n.sum())
     dev = op.device
     with torch.cuda.device(dev):
-        key = torch.as_tensor(codes_in_row_order(np.where(keep, codes, K), m.cell_of_row)).to(dev)   # left out: last
-        rows = torch.sort(key, stable=True).indices[:n_sel].to(torch.int32)
-        start = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-        start[1:] = torch.cumsum(torch.bincount(key, minlength=K + 1)[:K], 0)
+        n, rows, start = _row_list(codes, K, m.cell_of_row, dev)
+        n_sel = int(n.sum())
         ws = _device.workspace("markers", "prosstt_amd_markers_workspace_bytes", dev, n_sel, G, K, rows_per_block)
         ints = torch.empty((2, K, G), dtype=torch.int64, device=dev)
         sums = torch.empty((2, K, G), dtype=torch.float64, device=dev)
@@ -252,6 +266,13 @@ def _reference_index(groups, reference):
     return at[0]
 
 
+def _bad_method(method, allowed=METHODS):
+    if method in RANK_METHODS:
+        return ("method %r is a rank test: it needs the matrix, not the sums of a GroupMoments "
+                "(rank_genes_groups(counts, size_factors, labels, method=%r))" % (method, method))
+    return "method must be one of %s (got %r)" % (", ".join(allowed), method)
+
+
 def statistics(gm, reference="rest", method="t-test"):
     """``Statistics`` of a ``GroupMoments`` by the module docstring's formulas, host numpy in binary64.
 
@@ -260,7 +281,7 @@ def statistics(gm, reference="rest", method="t-test"):
     if not isinstance(gm, GroupMoments):
         raise TypeError("statistics takes a GroupMoments, not %s" % type(gm).__name__)
     if method not in METHODS:
-        raise ValueError("method must be one of %s (got %r)" % (", ".join(METHODS), method))
+        raise ValueError(_bad_method(method))
     ref = _reference_index(gm.groups, reference)
     n1 = gm.n.astype(np.float64)
     if np.any(gm.n < 2):
@@ -305,20 +326,29 @@ class RankGenesGroups(NamedTuple):
     moments: Any
 
 
-def rank_genes_groups(counts, size_factors=None, labels=None, *, reference="rest", method="t-test", n_genes=None,
-                      out="numpy"):
-    """The genes of every group ranked by their t statistic against ``reference`` (the module docstring's formulas):
-    ``RankGenesGroups``.
+def rank_genes_groups(counts, size_factors=None, labels=None, *, reference="rest", method="t-test", tie_correct=False,
+                      n_genes=None, out="numpy"):
+    """The genes of every group ranked by their score against ``reference`` (the module docstring's t, or for
+    ``method="wilcoxon"`` the z of ``prosstt_amd.ranks``): ``RankGenesGroups``.
 
     ``counts``, ``size_factors``, ``labels``, ``out``: as for ``group_moments`` (``out`` names where the moments stay; the
-    ranking is host numpy); or a ``GroupMoments`` as the only positional argument.  ``reference``: "rest" or a group;
-    ``method``: "t-test" or "t-test_overestim_var"; ``n_genes``: how many to keep per group, 1 .. genes (None: all).
+    ranking is host numpy); or a ``GroupMoments`` as the only positional argument (t-tests only: a rank test needs the
+    matrix).  ``reference``: "rest" or a group; ``method``: "t-test", "t-test_overestim_var" or "wilcoxon"; ``tie_correct``:
+    for "wilcoxon" against the rest, the variance with its tie term (``ranks.wilcoxon``); ``n_genes``: how many to keep per
+    group, 1 .. genes (None: all).
 
-    Raises what ``group_moments`` and ``statistics`` raise, and ValueError for ``n_genes`` out of range; the argument
-    checks come before any device use."""
-    if method not in METHODS:
-        raise ValueError("method must be one of %s (got %r)" % (", ".join(METHODS), method))
+    Raises what ``group_moments``, ``statistics``, ``ranks.rank_sums`` and ``ranks.wilcoxon`` raise, and ValueError for
+    ``n_genes`` out of range; the argument checks come before any device use."""
+    if method not in METHODS + RANK_METHODS:
+        raise ValueError(_bad_method(method, METHODS + RANK_METHODS))
+    ranked = method in RANK_METHODS
+    if not isinstance(tie_correct, (bool, np.bool_)):
+        raise ValueError("tie_correct must be True or False (got %r)" % (tie_correct,))
+    if tie_correct and not ranked:
+        raise ValueError("tie_correct belongs to method='wilcoxon', not to %r" % (method,))
     if isinstance(counts, GroupMoments):
+        if ranked:
+            raise ValueError(_bad_method(method))
         if size_factors is not None or labels is not None:
             raise ValueError("a GroupMoments comes without size factors and labels")
         gm, G = counts, counts.n_genes
@@ -330,10 +360,21 @@ def rank_genes_groups(counts, size_factors=None, labels=None, *, reference="rest
         raise ValueError("need an integer 1 <= n_genes <= genes = %d (got %r)" % (G, n_genes))
     if gm is None:
         groups, _ = encode_labels(labels, embed._counts(counts).N)
-        _reference_index(groups, reference)
+        ref = _reference_index(groups, reference)
+        if ranked and tie_correct and ref is not None:
+            raise ValueError(_ranks().TIE_CORRECT_NEEDS_REST)
         gm = group_moments(counts, size_factors, labels, out=out)
-    st = statistics(gm, reference, method)
+    if ranked:
+        st = _ranks().wilcoxon(_ranks().rank_sums(counts, size_factors, labels, reference=reference), gm,
+                               tie_correct=bool(tie_correct))
+    else:
+        st = statistics(gm, reference, method)
     names = np.argsort(-st.scores, axis=1, kind="stable")[:, :int(n_genes)]
     take = lambda a: np.take_along_axis(a, names, 1)                     # noqa: E731
     return RankGenesGroups(gm.groups, names.astype(np.int64), take(st.scores), take(st.logfoldchanges), take(st.pvals),
                            take(st.pvals_adj), take(st.pts), take(st.pts_rest), gm)
+
+
+def _ranks():
+    from . import ranks                 # (ranks imports this module)
+    return ranks

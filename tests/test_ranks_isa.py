@@ -1,0 +1,33 @@
+"""Properties of the ranks kernels' gfx950 code object (prosstt_amd/csrc/ranks/ranks.hip), read from the ISA hipcc writes
+with the library's own flags (cross-compiles without a GPU): every kernel is there, none uses scratch or spills a register,
+and there is no floating-point atomic."""
+import re
+
+import pytest
+
+import isa
+
+KERNELS = ["ranks_emit_kernelILb1E", "ranks_emit_kernelILb0E", "ranks_sort_kernel", "ranks_fold_kernel"]
+
+
+def test_every_kernel_is_listed():
+    text = isa.assembly("ranks")
+    names = set(re.findall(r"\.name:\s+(_Z\S*ranks_\S*_kernel\S*)", text))
+    names = {n for n in names if not n.endswith(".kd")}
+    assert len(names) == len(KERNELS), sorted(names)
+    for kernel in KERNELS:
+        assert any(kernel in n for n in names), kernel
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_no_scratch_and_no_spill(kernel):
+    text = isa.assembly("ranks")
+    assert isa.meta(text, kernel, "private_segment_fixed_size") == 0
+    assert isa.meta(text, kernel, "vgpr_spill_count") == 0
+    assert isa.meta(text, kernel, "sgpr_spill_count") == 0
+
+
+def test_no_floating_point_atomic():
+    text = isa.assembly("ranks")
+    found = sorted(set(m.group(0) for m in isa.FLOAT_ATOMIC.finditer(text)))
+    assert not found, found
