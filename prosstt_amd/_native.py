@@ -167,6 +167,14 @@ LATER_LIBRARIES = {
         "prosstt_amd_ranks_workspace_bytes": _int(i64, i64, i64, _ptr_to(u64)),
         "prosstt_amd_ranks_rank_sums": _int(vp, vp, i64, i64, i64, vp, vp, i64, vp, i64, i64, i64, vp, u64, vp, vp, vp),
     }, "prosstt_amd_ranks_last_error"),
+    # highly variable genes: sums of the counts clipped per gene, moments of x / s, and the chosen columns as a new matrix
+    "hvg": _Library(_path("PROSSTT_AMD_HVG_LIB", "libprosstt_amd_hvg.so"), "prosstt_amd_hvg.h", True, {
+        "prosstt_amd_hvg_last_error": _text,
+        "prosstt_amd_hvg_workspace_bytes": _int(i64, i64, _ptr_to(u64)),
+        "prosstt_amd_hvg_clipped_sums": _int(vp, vp, i64, i64, i64, vp, vp, u64, vp, vp, vp, vp),
+        "prosstt_amd_hvg_normalized_moments": _int(vp, vp, i64, i64, i64, vp, vp, u64, vp, vp, vp),
+        "prosstt_amd_hvg_gather_columns": _int(vp, vp, i64, i64, i64, vp, i64, vp, i64, vp),
+    }, "prosstt_amd_hvg_last_error"),
 }
 
 
