@@ -29,6 +29,11 @@ Louvain clusters of that neighbour graph on the device (what ``tl.louvain`` comp
     from prosstt_amd import cluster
     cl = cluster.louvain(nb)                          # cl.labels (cells,) int32, 0 the largest cluster; cl.modularity
 
+Which genes follow the structure of that graph, without labels (``metrics.morans_i`` / ``gearys_c``), and the smoothed matrix:
+
+    from prosstt_amd import autocorr
+    ac = autocorr.autocorrelation(X, sc, nb)          # ac.morans_i, ac.gearys_c, ac.z_i, ac.pvals_adj, ac.order
+
 or, for unmodified scripts that say ``from prosstt import ...``:
 
     import prosstt_amd; prosstt_amd.install_as_prosstt()

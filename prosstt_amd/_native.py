@@ -175,6 +175,13 @@ LATER_LIBRARIES = {
         "prosstt_amd_hvg_normalized_moments": _int(vp, vp, i64, i64, i64, vp, vp, u64, vp, vp, vp),
         "prosstt_amd_hvg_gather_columns": _int(vp, vp, i64, i64, i64, vp, i64, vp, i64, vp),
     }, "prosstt_amd_hvg_last_error"),
+    # spatial autocorrelation: sums over the edges of a cell graph of the log-normalised entries, and the smoothed matrix
+    "autocorr": _Library(_path("PROSSTT_AMD_AUTOCORR_LIB", "libprosstt_amd_autocorr.so"), "prosstt_amd_autocorr.h", True, {
+        "prosstt_amd_autocorr_last_error": _text,
+        "prosstt_amd_autocorr_workspace_bytes": _int(i64, i64, i64, _ptr_to(u64)),
+        "prosstt_amd_autocorr_gene_sums": _int(vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, i64, i32, vp, u64, vp, vp, vp, vp, vp),
+        "prosstt_amd_autocorr_smooth": _int(vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, i32, i32, vp, i64, vp),
+    }, "prosstt_amd_autocorr_last_error"),
 }
 
 

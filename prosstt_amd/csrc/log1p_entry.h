@@ -1,7 +1,7 @@
 // The float32 entry A[i][j] = log1p(X[i][j] * inv_size[i]) of the log-normalised count matrix, formed in registers: one
 // definition for every library that reads the matrix this way, so that their entries are equal to the bit.
-// Internal: included by embed/embed.hip, markers/markers.hip, ranks/ranks.hip and hvg/hvg.hip (which takes the product
-// scaled() alone), and not installed under include/.
+// Internal: included by embed/embed.hip, markers/markers.hip, ranks/ranks.hip, hvg/hvg.hip (which takes the product
+// scaled() alone) and autocorr/autocorr.hip, and not installed under include/.
 #pragma once
 
 #include <hip/hip_runtime.h>
