@@ -182,6 +182,12 @@ LATER_LIBRARIES = {
         "prosstt_amd_autocorr_gene_sums": _int(vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, i64, i32, vp, u64, vp, vp, vp, vp, vp),
         "prosstt_amd_autocorr_smooth": _int(vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, i32, i32, vp, i64, vp),
     }, "prosstt_amd_autocorr_last_error"),
+    # the count model's log-likelihood for several candidate (alpha, beta) per gene: what fit.count_model maximises
+    "fit": _Library(_path("PROSSTT_AMD_FIT_LIB", "libprosstt_amd_fit.so"), "prosstt_amd_fit.h", True, {
+        "prosstt_amd_fit_last_error": _text,
+        "prosstt_amd_fit_workspace_bytes": _int(i64, i64, i64, _ptr_to(u64)),
+        "prosstt_amd_fit_loglik": _int(vp, vp, i64, i64, i64, vp, vp, i64, vp, i64, vp, vp, i64, vp, u64, vp, vp, vp, vp),
+    }, "prosstt_amd_fit_last_error"),
 }
 
 

@@ -1,6 +1,6 @@
 // What a library that reads the int32 count matrix where it lies needs besides its kernels: the C ABI's error plumbing,
 // the refusals of a matrix argument, and the launch geometry of a "strip of genes over a range of rows" kernel.
-// Internal: included by stats/count_summary.hip, embed/embed.hip, knn/knn.hip, graph/graph.hip, layout/layout.hip, tsne/tsne.hip, dpt/dpt.hip, markers/markers.hip, cluster/cluster.hip, ranks/ranks.hip, hvg/hvg.hip and autocorr/autocorr.hip (knn to dpt and cluster read no
+// Internal: included by stats/count_summary.hip, embed/embed.hip, knn/knn.hip, graph/graph.hip, layout/layout.hip, tsne/tsne.hip, dpt/dpt.hip, markers/markers.hip, cluster/cluster.hip, ranks/ranks.hip, hvg/hvg.hip, autocorr/autocorr.hip and fit/fit.hip (knn to dpt and cluster read no
 // count matrix and use the error plumbing, cdiv, pad, aligned and the two refusals only), each a single translation unit, and not installed
 // under include/.  The including file defines ABI_EINVAL and ABI_EHIP (its header's error codes) first.
 // (prosstt_amd.hip keeps macros of its own: its ABI has an ENOMEM code and reports e.what().)
