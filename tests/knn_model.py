@@ -62,4 +62,31 @@ def duplicates(d, seed, distinct=40, copies=30):
 
 KINDS = {"gaussian": gaussian, "scaled": scaled,
          "lattice": lambda N, d, seed: lattice(N, seed, d),
-         "duplicates": lambda N, d, seed: duplicates(d, seed, distinct=N // 30)}
+         "duplicates": lambda N, d, seed: duplicates(d, seed, distinct=N // 30),
+         "copies100": lambda N, d, seed: duplicates(d, seed, distinct=N // 100, copies=100)}
+
+
+def tie_spans(P, k, seg=1024):
+    """(crosses, cut), two bool (N,) arrays, of the keys equal to T, the k-th smallest d2 of a row (self excluded), when
+    the row is walked in segments of ``seg`` consecutive candidates.  With need = k - (keys below T): crosses is True where
+    some segment after the first starts with 0 < (equal keys met so far) < need, so that the equal keys taken come from a
+    later segment after an earlier one supplied some but not all of them; cut is True where there are more keys equal to
+    T than need, so that which of them are taken decides the result."""
+    P = np.ascontiguousarray(P, dtype=np.float32)
+    N, d = P.shape
+    acc = np.zeros((N, N), np.float32)
+    for c in range(d):
+        t = P[:, None, c] - P[None, :, c]
+        acc += t * t
+    bits = acc.view(np.uint32).astype(np.int64)
+    bits[np.arange(N), np.arange(N)] = np.int64(1) << 40         # self: above every key
+    T = np.partition(bits, k - 1, axis=1)[:, k - 1]
+    need = k - (bits < T[:, None]).sum(axis=1)
+    equal = bits == T[:, None]
+    cut = equal.sum(axis=1) > need
+    starts = np.arange(seg, N, seg)
+    if starts.size == 0:
+        return np.zeros(N, bool), cut
+    so_far = np.cumsum(equal, axis=1)[:, starts - 1]             # equal keys before each later segment's start
+    crosses = np.any((so_far > 0) & (so_far < need[:, None]), axis=1)
+    return crosses, cut

@@ -23,6 +23,10 @@ assert REL_BOUND <= 1e-9
 CONNECTIVITY_CASES = [(3, 2), (63, 5), (64, 14), (65, 63), (257, 64), (257, 65), (257, 255), (1000, 14), (1000, 700),
                       (3001, 1024), (2000, 100)]
 CONNECTIVITY_CASES = [(N, k, 10, "tree") for N, k in CONNECTIVITY_CASES] + [(1200, 15, 3, "duplicates"), (1200, 15, 4, "lattice")]
+# degenerate rows wider than one slot of the 16 a lane keeps: twelve points a hundred times each.  k = 70: every row is all
+# zero over two slots (rho = 0, sigma = 2^-64 in the model); k = 130: the first positive distance sits in column 99, so
+# the minimum that gives rho comes from the second slot
+CONNECTIVITY_CASES += [(1200, 70, 3, "copies100"), (1200, 130, 3, "copies100")]
 
 
 def _cuda(array):
@@ -56,7 +60,13 @@ def test_connectivities_and_transitions_against_the_model(N, k, d, kind):
     np.testing.assert_array_equal(g.indices.cpu().numpy(), W.indices)
     per_row = np.diff(W.indptr)
     assert per_row.min() >= k and per_row.max() <= N - 1
-    if kind != "tree":
+    if kind == "copies100":
+        assert np.all(case["d2"][:, :min(k, 99)] == 0) and np.all(case["d2"][:, 99:] > 0)
+        if k < 100:
+            assert np.all(case["rho"] == 0) and np.all(case["sigma"] == 2.0 ** -64)
+        else:
+            assert np.all(case["rho"] == np.sqrt(case["d2"][:, 99].astype(np.float64)))
+    elif kind != "tree":
         assert np.any(case["d2"] == 0) and np.any(case["rho"] == 0 if kind == "duplicates" else case["rho"] > 0)
     t = graph.transitions(g)
     assert t.indptr.data_ptr() == g.indptr.data_ptr() and t.indices.data_ptr() == g.indices.data_ptr()

@@ -49,6 +49,20 @@ CASES = [
     (1200, 3, 15, None, None, "duplicates"),
     (1200, 50, 64, 7, (3, 1), "duplicates"),
 ]
+# Exact ties that span the select kernel's segments of 1024 candidates: at least 0.30 of the rows of each case below take
+# the keys equal to the k-th from a later segment after an earlier one supplied some but not all of them, with more equal
+# keys than places (knn_model.tie_spans; tests/test_knn_host.py asserts the shares, and that they are 0 in the four tie cases
+# above).  N = 2049 has one candidate in the third segment.
+SPANNING_TIE_CASES = [
+    (3001, 4, 15, None, (0, 0), "lattice"),
+    (3001, 4, 255, 7, (3, 1), "lattice"),
+    (3001, 4, 700, 64, None, "lattice"),
+    (3001, 4, 1024, "N", (3, 1), "lattice"),
+    (2049, 4, 15, None, None, "lattice"),
+    (3000, 3, 150, 64, (0, 0), "copies100"),
+]
+TIE_CASES = [c for c in CASES if c[5] in ("lattice", "duplicates")]
+CASES += SPANNING_TIE_CASES
 
 
 def _input(P, view):

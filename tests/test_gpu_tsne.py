@@ -24,6 +24,7 @@ import functools
 import numpy as np
 import pytest
 
+import graph_model
 import knn_model
 import layout_model
 import tsne_model
@@ -109,6 +110,19 @@ def test_degenerate_rows_and_status_bits():
     assert status == 0 and np.all(cond == 1.0 / 14) and np.all(beta == 2.0 ** 64)
     model_cond, model_beta = tsne_model.conditional(d2, 4.0)
     assert np.array_equal(cond, model_cond) and np.array_equal(beta, model_beta)
+    # rows wider than one slot of the 16 a lane keeps: twelve points a hundred times each.  k = 70: all zero over two
+    # slots, uniform rows; k = 130: 99 zeros, more than the perplexity, so beta runs to 2^64 and the rest of the row is 0
+    for k in (70, 130):
+        wide = graph_model.case(1200, k, 3, "copies100")
+        assert np.all(wide["d2"][:, :min(k, 99)] == 0) and np.all(wide["d2"][:, 99:] > 0)
+        cond, beta, status = _conditional(wide["idx"], wide["d2"], 20.0)
+        model_cond, model_beta = tsne_model.conditional(wide["d2"], 20.0)
+        assert np.all(model_beta == 2.0 ** 64)
+        if k == 70:
+            assert np.all(model_cond == 1.0 / 70)
+        else:
+            assert np.all(model_cond[:, :99] == 1.0 / 99) and np.all(model_cond[:, 99:] == 0)
+        assert status == 0 and np.array_equal(cond, model_cond) and np.array_equal(beta, model_beta)
     # every status bit by its bad value; the good rows are as before
     cs = tsne_model.case(65, 63, 20.0)
     good = _conditional(cs["idx"], cs["d2"], 20.0)[0]

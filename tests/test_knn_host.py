@@ -43,6 +43,33 @@ def test_model_resolves_ties_to_the_lower_index():
     assert tied > N // 2, tied
 
 
+def test_which_tie_cases_span_the_select_kernels_segments():
+    """The share of rows whose keys equal to the k-th come from more than one segment of 1024 candidates, the later one
+    after 0 < ties so far < need, while ties are cut at k: at least 0.30 in every case added for it (the smallest measured
+    was 0.37, lattice at N = 3001 and k = 255), and 0 in the four tie cases from before, which fit their ties into one
+    segment or cross none: they stay as small inputs and test_gpu_knn.SPANNING_TIE_CASES carry the running count."""
+    import test_gpu_knn
+    assert len(test_gpu_knn.TIE_CASES) == 5 and len(test_gpu_knn.SPANNING_TIE_CASES) == 6
+    for cases, spanning in ((test_gpu_knn.SPANNING_TIE_CASES, True), (test_gpu_knn.TIE_CASES, False)):
+        for N, d, k, _, _, kind in cases:
+            P = knn_model.KINDS[kind](N, d, 1000 * N + 10 * d + k)
+            crosses, cut = knn_model.tie_spans(P, k)
+            share = float(np.mean(crosses & cut))
+            print("%s N = %d, k = %d: %.3f of the rows cross a segment with ties cut at k" % (kind, N, k, share))
+            assert cut.any()
+            assert share >= 0.30 if spanning else share == 0.0, (N, d, k, kind, share)
+
+
+def test_tie_spans_on_a_hand_made_row():
+    # candidates on a line seen from cell 0, in segments of three: (self), 1, 1 | 4, 4, 4 | 4, 4, 9
+    P = np.array([[0], [1], [-1], [2], [-2], [2], [-2], [2], [3]], dtype=np.float32)
+    for k, crosses, cut in ((2, False, False), (3, False, True), (4, False, True), (5, False, True), (6, True, True),
+                            (7, True, False), (8, False, False)):
+        got = knn_model.tie_spans(P, k, seg=3)
+        assert (bool(got[0][0]), bool(got[1][0])) == (crosses, cut), k
+    assert not knn_model.tie_spans(P, 6, seg=1024)[0].any()
+
+
 def test_symmetric_bits():
     P = knn_model.scaled(300, 33, 3)
     idx, d2 = knn_model.model(P, 299)
