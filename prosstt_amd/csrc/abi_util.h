@@ -1,8 +1,10 @@
-// What a library that reads the int32 count matrix where it lies needs besides its kernels: the C ABI's error plumbing,
-// the refusals of a matrix argument, and the launch geometry of a "strip of genes over a range of rows" kernel.
-// Internal: included by stats/count_summary.hip, embed/embed.hip, knn/knn.hip, graph/graph.hip, layout/layout.hip, tsne/tsne.hip, dpt/dpt.hip, markers/markers.hip, cluster/cluster.hip, ranks/ranks.hip, hvg/hvg.hip, autocorr/autocorr.hip and fit/fit.hip (knn to dpt and cluster read no
-// count matrix and use the error plumbing, cdiv, pad, aligned and the two refusals only), each a single translation unit, and not installed
-// under include/.  The including file defines ABI_EINVAL and ABI_EHIP (its header's error codes) first.
+// What a library behind a C ABI needs besides its kernels: the error plumbing, the refusals of a matrix argument, and the
+// launch geometry of a "strip of genes over a range of rows" kernel (the host half of a strip kernel).  The device half is
+// strip_device.h (a lane's genes, its four counts of a row, the slab stores and fold); wave_reduce.h holds the wave sums.
+// Internal: included by every HIP library but the sampler (Makefile: the rows that list it), each a single translation
+// unit, and not installed under include/.  The libraries that read no count matrix (knn, graph, layout, tsne, dpt, cluster)
+// use the error plumbing, cdiv, pad, aligned and the two refusals only.
+// The including file defines ABI_EINVAL and ABI_EHIP (its header's error codes) first.
 // (prosstt_amd.hip keeps macros of its own: its ABI has an ENOMEM code and reports e.what().)
 #pragma once
 
@@ -72,8 +74,10 @@ inline int workspace_too_small(uint64_t have, size_t need)
 }
 
 // The grid of a strip kernel: blockIdx.x owns the genes [kStrip x, kStrip (x + 1)), blockIdx.y the rows
-// [rows_per_block y, rows_per_block (y + 1)).  All zeros when G == 0.  (The kernels' mapping of a lane to its four genes
-// stays written out in each: as a shared __device__ helper it changed count_summary_kernel's register allocation.)
+// [rows_per_block y, rows_per_block (y + 1)).  All zeros when G == 0.  (The mapping of a lane to its four genes is
+// strip_device.h's.  count_summary_kernel takes it for g0, the whole-strip test and its stores, with the same loops and
+// registers; inside its accumulate and rows4 the shared strip_gene changed the register allocation again, 122 / 124 VGPRs to
+// 114 / 112, and there the mapping stays written out.)
 struct StripGeometry {
     int64_t strips = 0, row_blocks = 0, rows_per_block = 0;
 };

@@ -23,6 +23,7 @@
 #define ABI_EINVAL PROSSTT_AMD_CLUSTER_EINVAL
 #define ABI_EHIP PROSSTT_AMD_CLUSTER_EHIP
 #include "../abi_util.h"
+#include "../wave_reduce.h"               // group_sum, wave_sum, wave_min
 
 #include <climits>
 #include <cmath>
@@ -51,14 +52,6 @@ unsigned stride_blocks(int64_t items)
 {
     const int64_t b = cdiv(items, kThreads);
     return (unsigned)(b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b));
-}
-
-template <int G>
-__device__ __forceinline__ int64_t group_sum(int64_t v)
-{
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // (begin, length) of row i, or an empty row and BAD_GRAPH

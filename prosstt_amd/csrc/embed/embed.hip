@@ -22,6 +22,7 @@
 #define ABI_EINVAL PROSSTT_AMD_EMBED_EINVAL
 #define ABI_EHIP PROSSTT_AMD_EMBED_EHIP
 #include "../abi_util.h"
+#include "../strip_device.h"              // the lane's genes, load_row4, for_lane_genes, fold_two_slabs
 #include "../log1p_entry.h"                 // entry(): the float32 log1p(x * inv), shared with markers/markers.hip
 
 namespace {
@@ -79,10 +80,10 @@ __global__ __launch_bounds__(kThreads) void embed_moments_kernel(const int32_t* 
 {
     const int tid = threadIdx.x;
     const int64_t gbase = (int64_t)blockIdx.x * kStrip;
-    const int64_t g0 = VEC ? gbase + 4 * tid : gbase + tid;
+    const int64_t g0 = strip_g0<VEC>(gbase, tid);
     const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
     const int64_t r1 = (r0 + rows_per_block < N) ? r0 + rows_per_block : N;
-    const bool full = gbase + kStrip <= G;
+    const bool full = strip_whole(gbase, G);
     double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
     int32_t neg = 0;
 #pragma unroll 2
@@ -90,16 +91,7 @@ __global__ __launch_bounds__(kThreads) void embed_moments_kernel(const int32_t* 
         const int32_t* rp = X + r * ld;
         const float inv = inv_size[r];
         int32_t x[4];
-        if (VEC && full) {
-            const int4 v = *reinterpret_cast<const int4*>(rp + g0);
-            x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int64_t g = VEC ? g0 + j : g0 + 256 * j;
-                x[j] = g < G ? rp[g] : 0;
-            }
-        }
+        load_row4<VEC>(x, rp, g0, G, full);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             neg |= x[j];
@@ -109,14 +101,10 @@ __global__ __launch_bounds__(kThreads) void embed_moments_kernel(const int32_t* 
         }
     }
     const size_t at = (size_t)blockIdx.y * (size_t)G;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t g = VEC ? g0 + j : g0 + 256 * j;
-        if (g < G) {
-            s1slab[at + g] = s1[j];
-            s2slab[at + g] = s2[j];
-        }
-    }
+    for_lane_genes<VEC>(g0, G, at, [&](int j, size_t i) {
+        s1slab[i] = s1[j];
+        s2slab[i] = s2[j];
+    });
     if (neg < 0) atomicOr(status, 1u);
 }
 
@@ -125,15 +113,7 @@ __global__ __launch_bounds__(kThreads) void embed_sum_moments_kernel(const doubl
                                                                      int64_t row_blocks, double* __restrict__ S1,
                                                                      double* __restrict__ S2)
 {
-    const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (g >= G) return;
-    double a = 0.0, b = 0.0;
-    for (int64_t k = 0; k < row_blocks; ++k) {
-        a += s1slab[k * G + g];
-        b += s2slab[k * G + g];
-    }
-    S1[g] = a;
-    S2[g] = b;
+    fold_two_slabs(s1slab, s2slab, G, row_blocks, S1, S2);
 }
 
 // ------------------------------------------------------------------------------------------------------------ A . W

@@ -17,6 +17,7 @@
 #define ABI_EINVAL PROSSTT_AMD_GRAPH_EINVAL
 #define ABI_EHIP PROSSTT_AMD_GRAPH_EHIP
 #include "../abi_util.h"
+#include "../wave_reduce.h"               // group_sum, wave_sum, wave_min
 
 #include <cmath>
 
@@ -46,21 +47,6 @@ int check_csr(int64_t N, int64_t nnz)
 }
 
 size_t half_workspace(int64_t N, int64_t k) { return pad((size_t)(2 * N * k) * 8); }
-
-template <int G>
-__device__ __forceinline__ double group_sum(double v)
-{
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_min(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-    return v;
-}
 
 // -------------------------------------------------------------------------------------------------------- memberships
 

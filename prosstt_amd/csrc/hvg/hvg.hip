@@ -22,6 +22,7 @@
 #define ABI_EINVAL PROSSTT_AMD_HVG_EINVAL
 #define ABI_EHIP PROSSTT_AMD_HVG_EHIP
 #include "../abi_util.h"
+#include "../strip_device.h"              // the lane's genes, load_row4, for_lane_genes, fold_two_slabs
 #include "../log1p_entry.h"                 // scaled(): the float32 x * inv that embed's log1p entry starts from
 
 namespace {
@@ -48,23 +49,6 @@ Geometry geometry(int64_t N, int64_t G)
     g.bytes = g.over + pad(cells * 4);
     g.m2 = pad(cells * 8);                           // (two binary64 slabs: less than the clipped pass's four)
     return g;
-}
-
-// The lane's four counts of one row.  VEC: genes g0 .. g0+3 (one 16-byte load when the strip is full); otherwise
-// g0 + 256*j (four coalesced 4-byte loads).  Genes >= G read nothing and count as 0.
-template <bool VEC>
-__device__ __forceinline__ void load_row(int32_t (&x)[4], const int32_t* __restrict__ rp, int64_t g0, int64_t G, bool full)
-{
-    if (VEC && full) {
-        const int4 v = *reinterpret_cast<const int4*>(rp + g0);
-        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t g = VEC ? g0 + j : g0 + 256 * j;
-            x[j] = g < G ? rp[g] : 0;
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------- clipped sums
@@ -106,16 +90,16 @@ __global__ __launch_bounds__(kThreads, 4) void hvg_clipped_kernel(const int32_t*
 {
     const int tid = threadIdx.x;
     const int64_t gbase = (int64_t)blockIdx.x * kStrip;
-    const int64_t g0 = VEC ? gbase + 4 * tid : gbase + tid;
+    const int64_t g0 = strip_g0<VEC>(gbase, tid);
     const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
     const int64_t r1 = (r0 + rows_per_block < N) ? r0 + rows_per_block : N;
-    const bool full = gbase + kStrip <= G;
+    const bool full = strip_whole(gbase, G);
 
     uint32_t t[4];
     ClipAcc a;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const int64_t g = VEC ? g0 + j : g0 + 256 * j;
+        const int64_t g = strip_gene<VEC>(g0, j);
         t[j] = g < G ? (uint32_t)threshold[g] : 0u;     // (a negative threshold: hvg_clipped_sum_kernel reports it)
         a.s1[j] = 0; a.s2lo[j] = 0; a.s2hi[j] = 0; a.over[j] = 0;
     }
@@ -126,21 +110,17 @@ __global__ __launch_bounds__(kThreads, 4) void hvg_clipped_kernel(const int32_t*
 #pragma unroll 1
     for (int64_t r = r0; r < r1; ++r) {
         int32_t x[4];
-        load_row<VEC>(x, X + r * ld, g0, G, full);
+        load_row4<VEC>(x, X + r * ld, g0, G, full);
         clip_add(x, t, a);
     }
 
     const size_t at = (size_t)blockIdx.y * (size_t)G;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t g = VEC ? g0 + j : g0 + 256 * j;
-        if (g < G) {
-            s.s1[at + g] = a.s1[j];
-            s.s2lo[at + g] = a.s2lo[j];
-            s.s2hi[at + g] = a.s2hi[j];
-            s.over[at + g] = a.over[j];
-        }
-    }
+    for_lane_genes<VEC>(g0, G, at, [&](int j, size_t i) {
+        s.s1[i] = a.s1[j];
+        s.s2lo[i] = a.s2lo[j];
+        s.s2hi[i] = a.s2hi[j];
+        s.over[i] = a.over[j];
+    });
     if (a.neg < 0) atomicOr(status, PROSSTT_AMD_HVG_NEGATIVE);
 }
 
@@ -191,17 +171,17 @@ __global__ __launch_bounds__(kThreads) void hvg_moments_kernel(const int32_t* __
 {
     const int tid = threadIdx.x;
     const int64_t gbase = (int64_t)blockIdx.x * kStrip;
-    const int64_t g0 = VEC ? gbase + 4 * tid : gbase + tid;
+    const int64_t g0 = strip_g0<VEC>(gbase, tid);
     const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
     const int64_t r1 = (r0 + rows_per_block < N) ? r0 + rows_per_block : N;
-    const bool full = gbase + kStrip <= G;
+    const bool full = strip_whole(gbase, G);
     double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
     int32_t neg = 0;
 #pragma unroll 1                            // (one row in flight, as in hvg_clipped_kernel: 0.78 ms; unrolled by 2 / 4: 0.89 / 0.98)
     for (int64_t r = r0; r < r1; ++r) {
         const float inv = inv_size[r];
         int32_t x[4];
-        load_row<VEC>(x, X + r * ld, g0, G, full);
+        load_row4<VEC>(x, X + r * ld, g0, G, full);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             neg |= x[j];
@@ -211,14 +191,10 @@ __global__ __launch_bounds__(kThreads) void hvg_moments_kernel(const int32_t* __
         }
     }
     const size_t at = (size_t)blockIdx.y * (size_t)G;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t g = VEC ? g0 + j : g0 + 256 * j;
-        if (g < G) {
-            s1slab[at + g] = s1[j];
-            s2slab[at + g] = s2[j];
-        }
-    }
+    for_lane_genes<VEC>(g0, G, at, [&](int j, size_t i) {
+        s1slab[i] = s1[j];
+        s2slab[i] = s2[j];
+    });
     if (neg < 0) atomicOr(status, PROSSTT_AMD_HVG_NEGATIVE);
 }
 
@@ -227,15 +203,7 @@ __global__ __launch_bounds__(kThreads) void hvg_moments_sum_kernel(const double*
                                                                    int64_t row_blocks, double* __restrict__ S1,
                                                                    double* __restrict__ S2)
 {
-    const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (g >= G) return;
-    double a = 0.0, b = 0.0;
-    for (int64_t k = 0; k < row_blocks; ++k) {
-        a += s1slab[k * G + g];
-        b += s2slab[k * G + g];
-    }
-    S1[g] = a;
-    S2[g] = b;
+    fold_two_slabs(s1slab, s2slab, G, row_blocks, S1, S2);
 }
 
 // ------------------------------------------------------------------------------------------------- gather columns

@@ -12,6 +12,7 @@
 #define ABI_EINVAL PROSSTT_AMD_LAYOUT_EINVAL
 #define ABI_EHIP PROSSTT_AMD_LAYOUT_EHIP
 #include "../abi_util.h"
+#include "../wave_reduce.h"               // group_sum, wave_sum, wave_min
 
 #include <cmath>
 
@@ -49,14 +50,6 @@ __device__ __forceinline__ int64_t negative_index(uint64_t base, uint64_t e, int
 {
     const uint64_t h = mix(base ^ (32ull * e + (uint64_t)s));
     return (int64_t)(((h >> 32) * (uint64_t)N) >> 32);
-}
-
-template <int G>
-__device__ __forceinline__ float group_sum(float v)
-{
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 template <int C, int G>

@@ -13,6 +13,7 @@
 #define ABI_EINVAL PROSSTT_AMD_MARKERS_EINVAL
 #define ABI_EHIP PROSSTT_AMD_MARKERS_EHIP
 #include "../abi_util.h"
+#include "../strip_device.h"              // the lane's genes, load_row4
 #include "../log1p_entry.h"                 // entry(): the float32 log1p(x * inv), shared with embed/embed.hip
 
 namespace {
@@ -109,23 +110,6 @@ struct Sums {
     int32_t neg = 0;
 };
 
-// The lane's four counts of one row: genes g0 .. g0 + 3 (WIDE: one 16-byte load of a whole strip; else VEC) or g0 + 256 j
-// (zeros past G).
-template <bool VEC, bool WIDE>
-__device__ __forceinline__ void load_row4(int32_t (&x)[4], const int32_t* __restrict__ rp, int64_t g0, int64_t G)
-{
-    if (WIDE) {
-        const int4 v = *reinterpret_cast<const int4*>(rp + g0);
-        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t g = VEC ? g0 + j : g0 + 256 * j;
-            x[j] = g < G ? rp[g] : 0;
-        }
-    }
-}
-
 __device__ __forceinline__ void add_row4(Sums& t, const int32_t (&x)[4], float inv)
 {
 #pragma unroll
@@ -194,8 +178,8 @@ __global__ __launch_bounds__(kThreads) void markers_pass_kernel(const int32_t* _
     const int4 e = table[blockIdx.y];               // (group, first, last): block-uniform, as are the row indices below
     const int tid = threadIdx.x;
     const int64_t gbase = (int64_t)blockIdx.x * kStrip;
-    const int64_t g0 = VEC ? gbase + 4 * tid : gbase + tid;
-    const bool full = gbase + kStrip <= G;
+    const int64_t g0 = strip_g0<VEC>(gbase, tid);
+    const bool full = strip_whole(gbase, G);
     Sums t;
     uint32_t flags = 0;
     if (VEC && full)
@@ -204,8 +188,8 @@ __global__ __launch_bounds__(kThreads) void markers_pass_kernel(const int32_t* _
         sum_rows<VEC, false>(t, flags, X, N, G, ld, inv_size, rows, e.y, e.z, g0);
     const size_t at = (size_t)blockIdx.y * (size_t)G;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t g = VEC ? g0 + j : g0 + 256 * j;
+    for (int j = 0; j < 4; ++j) {                   // (written out: see strip_device.h)
+        const int64_t g = strip_gene<VEC>(g0, j);
         if (g < G) {
             nzslab[at + g] = t.nz[j];
             csslab[at + g] = t.cs[j];

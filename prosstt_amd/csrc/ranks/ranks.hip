@@ -14,6 +14,7 @@
 #define ABI_EINVAL PROSSTT_AMD_RANKS_EINVAL
 #define ABI_EHIP PROSSTT_AMD_RANKS_EHIP
 #include "../abi_util.h"
+#include "../strip_device.h"              // the lane's column, load_row4
 #include "../log1p_entry.h"                 // entry(): the float32 log1p(x * inv), shared with embed/embed.hip
 #include "ranks_index.h"
 
@@ -52,23 +53,6 @@ Geometry geometry(int64_t n_sel, int64_t G, int64_t genes_per_pass)
 }
 
 // ------------------------------------------------------------------------------------------------------------- emit
-
-// The lane's four counts of one row: genes g .. g + 3 (WIDE: one 16-byte load inside a whole strip; else VEC) or g + 256 j
-// (zeros from gene `end` on).
-template <bool VEC, bool WIDE>
-__device__ __forceinline__ void load_row4(int32_t (&x)[4], const int32_t* __restrict__ rp, int64_t g, int64_t end)
-{
-    if (WIDE) {
-        const int4 v = *reinterpret_cast<const int4*>(rp + g);
-        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t gj = VEC ? g + j : g + 256 * j;
-            x[j] = gj < end ? rp[gj] : 0;
-        }
-    }
-}
 
 // The keys of the positions [q0, q0 + nrows) over the lane's four genes, into the tile.  Returns the or of the counts.
 template <bool VEC, bool WIDE>
@@ -149,10 +133,10 @@ __global__ __launch_bounds__(kThreads) void ranks_emit_kernel(const int32_t* __r
         }
         group_sh[tid] = (uint16_t)left;
     }
-    const int col = VEC ? 4 * tid : tid;
+    const int col = strip_col<VEC>(tid);
     const int64_t g = gbase + col;
     int32_t neg;
-    if (VEC && gbase + kStrip <= g_end)
+    if (VEC && strip_whole(gbase, g_end))
         neg = fill_tile<VEC, true>(tile, flags, X, N, ld, inv_size, rows, q0, nrows, g, col, g_end);
     else
         neg = fill_tile<VEC, false>(tile, flags, X, N, ld, inv_size, rows, q0, nrows, g, col, g_end);

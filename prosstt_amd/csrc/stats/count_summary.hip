@@ -20,6 +20,7 @@
 #define ABI_EINVAL PROSSTT_AMD_STATS_EINVAL
 #define ABI_EHIP PROSSTT_AMD_STATS_EHIP
 #include "../abi_util.h"
+#include "../strip_device.h"              // the lane's genes, for_lane_genes
 
 namespace {
 
@@ -60,6 +61,7 @@ struct Acc {
 };
 
 // The sums of four rows of the lane's four genes (see rows4).  x^2 + s2lo is one v_mad_u64_u32, whose carry-out feeds s2hi.
+// (Here and in rows4 the gene of slot j stays written out: see strip_device.h.)
 template <bool VEC, bool MASK>
 __device__ __forceinline__ void accumulate(const uint32_t (&x)[4][4], int nrows, int64_t G, int64_t g0, Acc& a, uint64_t p[4])
 {
@@ -143,8 +145,8 @@ __global__ __launch_bounds__(kThreads, 4) void count_summary_kernel(const int32_
     const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
     const int64_t r1 = (r0 + rows_per_block < N) ? r0 + rows_per_block : N;
     const int64_t gbase = strip * kStrip;
-    const int64_t g0 = VEC ? gbase + 4 * tid : gbase + tid;
-    const bool full_strip = gbase + kStrip <= G;
+    const int64_t g0 = strip_g0<VEC>(gbase, tid);
+    const bool full_strip = strip_whole(gbase, G);
 
     Acc a;
 #pragma unroll
@@ -167,16 +169,12 @@ __global__ __launch_bounds__(kThreads, 4) void count_summary_kernel(const int32_
     }
 
     const size_t at = (size_t)blockIdx.y * (size_t)G;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t g = VEC ? g0 + j : g0 + 256 * j;
-        if (g < G) {
-            s.s1[at + g] = a.s1[j];
-            s.s2lo[at + g] = a.s2lo[j];
-            s.s2hi[at + g] = a.s2hi[j];
-            s.z[at + g] = a.z[j];
-        }
-    }
+    for_lane_genes<VEC>(g0, G, at, [&](int j, size_t i) {
+        s.s1[i] = a.s1[j];
+        s.s2lo[i] = a.s2lo[j];
+        s.s2hi[i] = a.s2hi[j];
+        s.z[i] = a.z[j];
+    });
     if (a.neg < 0) atomicOr(status, 1u);
 }
 

@@ -19,6 +19,7 @@
 #define ABI_EINVAL PROSSTT_AMD_TSNE_EINVAL
 #define ABI_EHIP PROSSTT_AMD_TSNE_EHIP
 #include "../abi_util.h"
+#include "../wave_reduce.h"               // group_sum, wave_sum, wave_min
 
 #include <cmath>
 
@@ -82,27 +83,6 @@ Plan make_plan(int64_t N, int c, int slabs)
     p.zb_off = p.abs_off + pad(per_row * c);
     p.bytes = p.zb_off + pad((size_t)kZBlocks * 8);
     return p;
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_min(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-    return v;
 }
 
 // ---------------------------------------------------------------------------------------------------------- affinities
