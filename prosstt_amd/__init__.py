@@ -34,6 +34,13 @@ Which genes follow the structure of that graph, without labels (``metrics.morans
     from prosstt_amd import autocorr
     ac = autocorr.autocorrelation(X, sc, nb)          # ac.morans_i, ac.gearys_c, ac.z_i, ac.pvals_adj, ac.order
 
+The way back from counts to the simulator's inputs: the count model's alpha and beta per gene, and the tree's means and
+densities from cells that have a branch and a pseudotime:
+
+    from prosstt_amd import fit, trends
+    tr = trends.expression_trends(X, sc, t, pt, br)   # tr.means (nodes, genes), tr.density, tr.to_tree()
+    f = fit.count_model(X, sc, tr.labels, tr.means)   # f.alpha, f.beta
+
 or, for unmodified scripts that say ``from prosstt import ...``:
 
     import prosstt_amd; prosstt_amd.install_as_prosstt()

@@ -188,6 +188,12 @@ LATER_LIBRARIES = {
         "prosstt_amd_fit_workspace_bytes": _int(i64, i64, i64, _ptr_to(u64)),
         "prosstt_amd_fit_loglik": _int(vp, vp, i64, i64, i64, vp, vp, i64, vp, i64, vp, vp, i64, vp, u64, vp, vp, vp, vp),
     }, "prosstt_amd_fit_last_error"),
+    # expression trends: exact integer sums of the cells around every node of the lineage tree, by a node-by-cell weight matrix
+    "trends": _Library(_path("PROSSTT_AMD_TRENDS_LIB", "libprosstt_amd_trends.so"), "prosstt_amd_trends.h", True, {
+        "prosstt_amd_trends_last_error": _text,
+        "prosstt_amd_trends_workspace_bytes": _int(i64, i64, i64, i64, _ptr_to(u64)),
+        "prosstt_amd_trends_node_sums": _int(vp, vp, i64, i64, i64, vp, vp, vp, i64, i64, i64, vp, u64, vp, vp, vp),
+    }, "prosstt_amd_trends_last_error"),
 }
 
 
