@@ -123,7 +123,8 @@ int prosstt_amd_run_plan(const int32_t* row_of_cell, int64_t N, int64_t rows, in
 
 /*
  * The same words as the preparation kernel of the LAST prosstt_amd_sample_counts call on this ctx wrote them (N + 4 of
- * them; at most `cap` are copied, *total receives their number, *strip_cells the strip length of that launch).  For
+ * them; at most `cap` are copied, *total receives their number, *strip_cells the strip length of that launch's bulk
+ * class: prosstt_amd_last_strip_plan in prosstt_amd_plan.h).  For
  * tests and diagnostics: it synchronises and copies.  Valid until the next call on the ctx.
  */
 int prosstt_amd_last_run_plan(prosstt_amd_ctx* ctx, uint32_t* words, int64_t cap, int64_t* total, int32_t* strip_cells);

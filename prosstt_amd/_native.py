@@ -1,6 +1,6 @@
 """
 ctypes binding of libprosstt_amd.so (include/prosstt_amd.h) and of the libraries beside it: each is described once in
-LIBRARIES, ADDED_LIBRARIES or LATER_LIBRARIES, and load / check do the rest.
+LIBRARIES, ADDED_LIBRARIES or LATER_LIBRARIES (the sampler's later entry points in SAMPLER_LATER), and load / check do the rest.
 
 There is NO CPU fallback: if the library is missing, or no gfx950 device is
 visible, every numeric entry point of the package raises.  torch is used only
@@ -197,6 +197,15 @@ LATER_LIBRARIES = {
 }
 
 
+# Entry points of the sampler library declared after tests/test_native_libraries.py pinned its census of prosstt_amd.h:
+# (their header, symbol -> prototype), declared by ``load`` beside the sampler's row; tests/test_strip_plan_host.py checks
+# them against the header and the built library.
+SAMPLER_LATER = ("prosstt_amd_plan.h", {
+    "prosstt_amd_strip_plan": _int(i64, i32, i32, i32, i32, vp, _ptr_to(i32), _ptr_to(i32), _ptr_to(i32)),
+    "prosstt_amd_last_strip_plan": _int(vp, vp, _ptr_to(i32), _ptr_to(i32), _ptr_to(i32)),
+})
+
+
 def _library(name):
     for table in (LIBRARIES, ADDED_LIBRARIES):
         if name in table:
@@ -231,7 +240,8 @@ def load(name="sampler"):
                 # exchangeable, and torch's own is the combination the wheel was built against.
                 import torch  # noqa: F401
             L = ctypes.CDLL(lib.path)
-            for symbol, (restype, argtypes) in lib.symbols.items():
+            symbols = dict(lib.symbols, **SAMPLER_LATER[1]) if name == "sampler" else lib.symbols
+            for symbol, (restype, argtypes) in symbols.items():
                 fn = getattr(L, symbol)
                 fn.restype = restype
                 if argtypes is not None:

@@ -45,7 +45,7 @@ struct HeavyLds {
 // the regions of a hot gene tile list beyond that (dealt out to the waves 64 at a time), and the regions whose list or
 // segment was too small: those are redone here sample by sample instead -- slow, but any parameter set stays correct.
 __global__ __launch_bounds__(kHeavyBlock) void sample_counts_heavy_kernel(
-    const HeavyList* __restrict__ heavy_ptr, uint32_t regions, int32_t strips, int32_t strip_cells,
+    const HeavyList* __restrict__ heavy_ptr, uint32_t regions, StripPlan plan,
     const float* __restrict__ means, int64_t rows,
     int32_t G, const int32_t* __restrict__ row_of_cell, const float* __restrict__ scal,
     const float* __restrict__ ga, const float* __restrict__ gbm1, int64_t N, uint32_t k0, uint32_t k1,
@@ -75,8 +75,31 @@ __global__ __launch_bounds__(kHeavyBlock) void sample_counts_heavy_kernel(
         seg_first[lane] = x - mine;
         if (lane == 63) seg_first[kSegs] = x;
     }
+    // the classes of the stream kernel's strip plan, as region_origin (below) reads them: thread k writes class k
+    // (a class that is not there: no cells, behind the last block)
+    struct ClassRec { int32_t first_cell, end_cell; uint32_t first_block, groups, groups_rcp, log2_len, pad[2]; };
+    __shared__ __attribute__((aligned(16))) ClassRec cls_tab[kPlanClasses];
+    if (tid < kPlanClasses) {
+        // (every class is read first and chosen by the lane's number without a branch: four divisions side by side, not one
+        // after the other in front of the block's barrier)
+        static_assert(kPlanClasses == 4, "spelled out below");
+        const StripClass c0 = plan.c[0], c1 = plan.c[1], c2 = plan.c[2], c3 = plan.c[3];
+        const int32_t end_all = plan.c[4].first_cell;
+        const int32_t first = tid == 0 ? c0.first_cell : (tid == 1 ? c1.first_cell : (tid == 2 ? c2.first_cell : c3.first_cell));
+        const int32_t end = tid == 0 ? c1.first_cell : (tid == 1 ? c2.first_cell : (tid == 2 ? c3.first_cell : end_all));
+        const int32_t len = tid == 0 ? c0.strip_cells : (tid == 1 ? c1.strip_cells : (tid == 2 ? c2.strip_cells : c3.strip_cells));
+        const int32_t fb = tid == 0 ? c0.first_block : (tid == 1 ? c1.first_block : (tid == 2 ? c2.first_block : c3.first_block));
+        const uint32_t sh = (uint32_t)__builtin_ctz((uint32_t)len);                      // (lengths are powers of two)
+        const int32_t strips = (end - first + len - 1) >> sh;
+        const uint32_t g = strips > 4 ? (uint32_t)(strips + 3) / 4u : 1u;
+        ClassRec c;
+        c.first_cell = first; c.end_cell = end; c.first_block = (uint32_t)fb;
+        c.groups = g;
+        c.groups_rcp = 0xffffffffu / g + ((g & (g - 1u)) == 0u ? 1u : 0u);                 // floor(2^32 / g) for g > 1
+        c.log2_len = sh; c.pad[0] = c.pad[1] = 0u;
+        cls_tab[tid] = c;
+    }
     __syncthreads();
-    const int32_t groups = (strips + 3) / 4;
     const uint32_t waves = gridDim.x * (kHeavyBlock / 64);
     // chunk -> (segment, first entry): the last segment whose first chunk is not behind it (wave-uniform)
     auto locate = [&](uint32_t chunk, uint32_t& seg, uint32_t& first) __attribute__((always_inline)) {
@@ -87,14 +110,25 @@ __global__ __launch_bounds__(kHeavyBlock) void sample_counts_heavy_kernel(
         seg = lo;
         first = (chunk - seg_first[lo]) << 6;
     };
-    // blk / groups for blk < 2^32: the estimate by the rounded-down reciprocal is the quotient or one below it (an integer
-    // division is ~30 instructions on this chip, and the kernel is bound by what it issues)
-    const uint32_t groups_rcp = groups > 1 ? (uint32_t)(0x100000000ull / (uint64_t)(uint32_t)groups) : 0u;
-    auto tile_of = [&](uint32_t blk) __attribute__((always_inline)) -> int32_t {
-        if (groups <= 1) return (int32_t)blk;
-        uint32_t q = __umulhi(blk, groups_rcp);
-        q += (blk - q * (uint32_t)groups >= (uint32_t)groups) ? 1u : 0u;
-        return (int32_t)q;
+    // region -> (gene tile, first cell, cells of its strip): the map of the stream kernel's launch (k3::strip_of_region is
+    // the rule), here per lane: the class by three compares with the classes' first blocks, its numbers from cls_tab.
+    // blk / groups for blk < 2^32 by the rounded-down reciprocal is the quotient or one below it (an integer division is
+    // ~30 instructions on this chip, and the kernel is bound by what it issues).
+    const uint32_t fb1 = (uint32_t)plan.c[1].first_block, fb2 = (uint32_t)plan.c[2].first_block, fb3 = (uint32_t)plan.c[3].first_block;
+    struct Origin { int32_t tile_g, n0, cells; };
+    auto region_origin = [&](uint32_t r) __attribute__((always_inline)) -> Origin {
+        const uint32_t blk = r >> 2;
+        const uint32_t cls = (blk >= fb1 ? 1u : 0u) + (blk >= fb2 ? 1u : 0u) + (blk >= fb3 ? 1u : 0u);
+        const ClassRec c = cls_tab[cls];
+        const uint32_t local = blk - c.first_block;
+        uint32_t q = __umulhi(local, c.groups_rcp);
+        q += (local - q * c.groups >= c.groups) ? 1u : 0u;
+        q = c.groups > 1u ? q : local;
+        Origin o;
+        o.tile_g = (int32_t)q;
+        o.n0 = c.first_cell + (int32_t)(((local - q * c.groups) * 4u + (r & 3u)) << c.log2_len);
+        o.cells = c.end_cell - o.n0 < (1 << c.log2_len) ? c.end_cell - o.n0 : (1 << c.log2_len);
+        return o;
     };
 
     int hg_top = 0, hp_top = 0, hw_top = 0;      // wave-uniform
@@ -426,11 +460,13 @@ __global__ __launch_bounds__(kHeavyBlock) void sample_counts_heavy_kernel(
         {
             const int sub = lane >> 4, sl = lane & 15;
             const uint4* const dense4 = reinterpret_cast<const uint4*>(heavy.dense);
-            struct Step { uint32_t cnt; uint4 d4; };
+            // (a step's origin is looked up a step ahead, with its loads: the table reads are not waited for where they are used)
+            struct Step { uint32_t cnt; uint4 d4; Origin o; };
             auto load_step = [&](uint64_t r0) __attribute__((always_inline)) -> Step {
                 Step S;
                 S.cnt = 0u; S.d4 = make_uint4(0u, 0u, 0u, 0u);
                 const uint64_t r = r0 + (uint64_t)sub * drawers;
+                S.o = region_origin((uint32_t)r);
                 if (r < (uint64_t)regions) {
                     S.cnt = heavy.count[r] & 0xffffu;
                     S.d4 = dense4[r * (kDense / 2) + (uint32_t)sl];
@@ -439,13 +475,10 @@ __global__ __launch_bounds__(kHeavyBlock) void sample_counts_heavy_kernel(
             };
             Step nxt = load_step(rank);
             for (uint64_t r0 = rank; r0 < (uint64_t)regions; r0 += 4ull * drawers) {
-                const uint32_t r = (uint32_t)(r0 + (uint64_t)sub * drawers);
                 const Step cur = nxt;
                 nxt = load_step(r0 + 4ull * drawers);
                 const uint32_t cnt = cur.cnt > heavy.cap ? 0u : cur.cnt;       // (above the cap: the region is redone as a whole)
-                const int32_t blk = (int32_t)(r >> 2);
-                const int32_t tile_g = tile_of((uint32_t)blk);
-                const int32_t n0 = ((blk - tile_g * groups) * 4 + (int32_t)(r & 3u)) * strip_cells;
+                const int32_t tile_g = cur.o.tile_g, n0 = cur.o.n0;
                 push_entries(2u * (uint32_t)sl < cnt, n0 + (int32_t)(cur.d4.x >> 8), tile_g * kTileG + (int32_t)(cur.d4.x & 255u), __uint_as_float(cur.d4.y));
                 push_entries(2u * (uint32_t)sl + 1u < cnt, n0 + (int32_t)(cur.d4.z >> 8), tile_g * kTileG + (int32_t)(cur.d4.z & 255u), __uint_as_float(cur.d4.w));
             }
@@ -485,11 +518,12 @@ __global__ __launch_bounds__(kHeavyBlock) void sample_counts_heavy_kernel(
         const uint32_t r_end = (wrank + 1u) * per_walker < regions ? (wrank + 1u) * per_walker : regions;
         const uint32_t rl = (uint32_t)lane >> 2, s0 = (uint32_t)lane & 3u;
         static_assert(kWalkSlots <= 12, "three slots per lane");
-        struct WStep { uint32_t n_walks; f32x4_t st[3]; uint32_t id[3]; };
+        struct WStep { uint32_t n_walks; f32x4_t st[3]; uint32_t id[3]; Origin o; };
         auto load_wstep = [&](uint32_t rb) __attribute__((always_inline)) -> WStep {
             WStep S;
             S.n_walks = 0u;
             const uint32_t r = rb + rl;
+            S.o = region_origin(r);
 #pragma unroll
             for (int j = 0; j < 3; ++j) { S.st[j] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f}; S.id[j] = 0u; }
             if (r < r_end) {
@@ -509,10 +543,7 @@ __global__ __launch_bounds__(kHeavyBlock) void sample_counts_heavy_kernel(
         for (uint32_t rb = wrank * per_walker; rb < r_end; rb += 16u) {
             const WStep cur = wn;
             wn = load_wstep(rb + 16u);
-            const uint32_t r = rb + rl;
-            const int32_t blk = (int32_t)(r >> 2);
-            const int32_t tile_g = tile_of((uint32_t)blk);
-            const int32_t n0 = ((blk - tile_g * groups) * 4 + (int32_t)(r & 3u)) * strip_cells;
+            const int32_t tile_g = cur.o.tile_g, n0 = cur.o.n0;
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 const uint32_t slot = s0 + 4u * (uint32_t)j;
@@ -521,17 +552,17 @@ __global__ __launch_bounds__(kHeavyBlock) void sample_counts_heavy_kernel(
             }
         }
     }
-    // Regions whose list or segment was too small: every sample of the region (strip_cells x 256 of the matrix) goes
+    // Regions whose list or segment was too small: every sample of the region (its strip's cells x 256 of the matrix) goes
     // through the classification here, 64 at a time: slow (the streaming kernel's own results are recomputed), but any
     // parameter set stays correct and only those regions pay
     {
         const uint32_t n_ovf = heavy.seg_cnt[kSegs];
         for (uint32_t i = wave_id; i < n_ovf; i += waves) {
             const uint32_t r = heavy.ovf_regions[i];
-            const int32_t blk = (int32_t)(r >> 2);
-            const int32_t tg = tile_of((uint32_t)blk);
-            const int64_t nb = (int64_t)((blk - tg * groups) * 4 + (int32_t)(r & 3u)) * strip_cells;
-            for (int32_t c = 0; c < strip_cells && nb + c < N; ++c)
+            const Origin o = region_origin(r);
+            const int32_t tg = o.tile_g;
+            const int64_t nb = o.n0;
+            for (int32_t c = 0; c < o.cells; ++c)
                 for (int j = 0; j < 4; ++j) {
                     const int32_t g = tg * kTileG + j * 64 + lane;
                     from_start(g < G, (int32_t)(nb + c), g);

@@ -38,6 +38,11 @@
 //   serialises them); the walks still running when the strip has nothing else to do travel there with their
 //   state; sample_counts_heavy_kernel (k3_heavy.h) draws and continues them afterwards.
 //
+// Which strip a wave takes is the launch's strip plan (StripPlan, strip_plan, strip_of_region below): a large launch runs
+// 128-cell strips first and about one residency of blocks each of 64-, 32- and 16-cell strips last, so that the fixed
+// cost of a strip is paid per 128 cells for 85 % of the headline workload and the launch still ends on short blocks
+// (-2.7 % of the kernel against uniform 64-cell strips: profiles/r18_ablation.txt); a small launch is uniform, as ever.
+//
 // P(X = 0): the hardware's v_rcp/v_log/v_exp ARE the definition (prnb_device.h: hw_p0), so
 // stage 2 needs no error margins and no sample is given up because it came close to a threshold (PRNB-4
 // defined P(X = 0) in polynomial arithmetic and paid for margins, a give-up list and K3h redo walks: -5 % of the
@@ -61,7 +66,7 @@ namespace k3 {
 
 constexpr int kBlock = 256;        // 4 waves
 constexpr int kTileG = 256;        // genes per wave pass: 64 lanes x 4
-constexpr int kStripCells = 128;   // most cells per wave (pos keeps the cell in 7 bits); the host launches 64
+constexpr int kStripCells = 128;   // most cells per wave (pos keeps the cell in 7 bits): the bulk of a graded plan; a uniform launch has 64 or fewer
 constexpr int kS1Cap = 192;        // < 64 left over + 128 pushed by half a pass (two samples per lane)
 constexpr int kS2Cap = 104;        // < 40 left over + 64 pushed by one stage-2 pass
 constexpr int kS2Run = 40;         // stage 3 runs while S2 holds at least this many entries (with eight terms per pass: 32 +0.9 %, 24 +4 %, 16 +7 %, 44 and 48 +0.7 %: profiles/r05_ablation.txt)
@@ -116,6 +121,106 @@ __host__ __device__ inline uint32_t run_word(const int32_t* row_of_cell, int64_t
         prev = r;
     }
     return len | (runs << 16);
+}
+
+// The strip plan: which cells every wave of a launch takes.  A launch is up to kPlanClasses classes of strips, each a range
+// of cells cut into strips of one length; blocks are numbered class by class, and within a class tile-major in groups of
+// four adjacent strips (adjacent blocks share the gene tile: L2 reuse of the mean tensor's column slice and of the
+// per-gene parameters).  The first class holds nearly all cells in long strips, whose fixed cost per strip (prologue, drain
+// on few lanes, a block's LDS and wave slots waiting for its slowest wave) is small; the classes behind it are about one
+// residency of blocks each, of half, a quarter and an eighth of that length, so that the launch ends on blocks that are
+// short: the time during which CUs hold fewer blocks than they could is that of the shortest class.
+// Results are pure functions of (sample, seed, global cell, gene): the plan changes no count.
+constexpr int kPlanClasses = 4;
+constexpr int kPlanAlign = 64;     // class boundaries are multiples of this: a wave of the preparation kernel lies in one class
+constexpr int kPlanMinStrip = 8;   // no class has shorter strips
+struct StripClass { int32_t first_cell, strip_cells, first_block; };
+struct StripPlan {
+    int32_t classes, tiles_g;
+    StripClass c[kPlanClasses + 1];    // c[classes ..] = {N, 1, blocks of the launch}
+};
+
+// The plan of a call of N cells x G genes on a device that holds `resident` blocks of the stream kernel at once.
+// The length of a uniform launch: 64 cells, halved while it would have fewer than 4 * 5 * 1024 blocks (forced_cells = 8,
+// 16, 32 or 64 sets it instead; 128 stands for 64 here).  A uniform launch of fewer than 4 * resident blocks stays that one class; a larger one
+// (or any, with taper > 0, which is then the residency) is graded: its bulk length is twice the uniform one where that
+// is 64 by the rule, not forced (128-cell strips halve the fixed cost per cell and are slower only by the tail they leave,
+// which the short classes take away), and classes of half, a quarter, an eighth of the bulk length follow it (none under
+// kPlanMinStrip cells; at most max_classes classes in all; 0: kPlanClasses), each of resident * 4 * length / tiles cells
+// rounded to the nearest multiple of kPlanAlign and at least that; the bulk class is what they leave, rounded down to a
+// multiple of its strip length and of kPlanAlign (a short class that would leave it not one strip is not made, nor the
+// ones behind it), and the last class takes the remainder of N.
+__host__ __device__ inline StripPlan strip_plan(int64_t N, int32_t G, int32_t resident, int32_t forced_cells, int32_t taper, int32_t max_classes)
+{
+    const int64_t n = N > 0 ? N : 0;
+    const int64_t tiles = ((int64_t)(G > 0 ? G : 0) + kTileG - 1) / kTileG;
+    int64_t L = 64;                        // measured best for a uniform launch on C3 (128: +1.7 %, 32: +2.7 %)
+    while (L > 8 && ((n + L - 1) / L) * tiles < 4 * 5 * 1024) L /= 2;
+    if (forced_cells == 8 || forced_cells == 16 || forced_cells == 32 || forced_cells == 64) L = forced_cells;
+    if (forced_cells == kStripCells) L = 64;      // (128 is the bulk of a graded plan only)
+    const int64_t uniform_blocks = (((n + L - 1) / L + 3) / 4) * tiles;
+    const int64_t R = taper > 0 ? taper : resident;
+    const int most = max_classes >= 1 && max_classes <= kPlanClasses ? max_classes : kPlanClasses;
+    int64_t size[kPlanClasses] = {n, 0, 0, 0};
+    int K = 1;
+    if (taper > 0 || (resident > 0 && uniform_blocks >= 4 * (int64_t)resident)) {
+        const int64_t uniform_len = L;
+        if (L == 64 && forced_cells != 64) L = kStripCells;
+        const int64_t align = L > kPlanAlign ? L : kPlanAlign;
+        int64_t shorts = 0;
+        while (K < most && (L >> K) >= kPlanMinStrip) {
+            int64_t s = ((R * 4 * (L >> K) / (tiles > 0 ? tiles : 1) + kPlanAlign / 2) / kPlanAlign) * kPlanAlign;
+            if (s < kPlanAlign) s = kPlanAlign;
+            if (n - (shorts + s) < align) break;
+            size[K++] = s;
+            shorts += s;
+        }
+        if (K > 1) size[0] = ((n - shorts) / align) * align;
+        else L = uniform_len;
+    }
+    StripPlan p;
+    p.classes = K;
+    p.tiles_g = (int32_t)tiles;
+    int64_t cell = 0, block = 0;
+    for (int k = 0; k <= kPlanClasses; ++k) {
+        const int64_t len = k < K ? L >> k : 1;
+        const int64_t cells = k + 1 < K ? size[k] : n - cell;     // (the last class: the remainder; behind it: nothing)
+        p.c[k].first_cell = (int32_t)cell;
+        p.c[k].strip_cells = (int32_t)len;
+        p.c[k].first_block = (int32_t)(block < 0x7fffffff ? block : 0x7fffffff);     // (the host refuses launches of 2^29 blocks)
+        cell += cells;
+        block += (((cells + len - 1) / len + 3) / 4) * tiles;
+    }
+    return p;
+}
+
+// The strip of region r = 4 * block + wave of a launch by plan p: its gene tile, first cell, cells (0: the block's group
+// has no strip there) and the strip length of its class.
+struct StripAt { int32_t tile_g, cells, strip_cells; int64_t n0; };
+__host__ __device__ inline StripAt strip_of_region(const StripPlan& p, uint32_t region)
+{
+    const int32_t blk = (int32_t)(region >> 2);
+    // (every class is read before the choice, none inside it: the compiler otherwise merges the reads of the branches into
+    // one read at a computed address, and a kernel's plan -- an argument, in registers -- into a copy in scratch memory)
+    static_assert(kPlanClasses == 4, "spelled out below");
+    const StripClass c0 = p.c[0], c1 = p.c[1], c2 = p.c[2], c3 = p.c[3];
+    const int32_t end_all = p.c[4].first_cell;
+    StripClass c = c0;
+    int32_t end = c1.first_cell;
+    if (blk >= c1.first_block) { c = c1; end = c2.first_cell; }      // (a class that is not there starts behind the launch's last block)
+    if (blk >= c2.first_block) { c = c2; end = c3.first_cell; }
+    if (blk >= c3.first_block) { c = c3; end = end_all; }
+    const int32_t first = c.first_cell, len = c.strip_cells, fb = c.first_block;
+    const int32_t strips = (end - first + len - 1) >> __builtin_ctz((uint32_t)len);      // (lengths are powers of two)
+    const int32_t groups = strips > 4 ? (strips + 3) / 4 : 1;
+    const int32_t local = blk - fb;
+    StripAt at;
+    at.tile_g = local / groups;
+    at.strip_cells = len;
+    const int32_t strip = (local - at.tile_g * groups) * 4 + (int32_t)(region & 3u);
+    at.n0 = (int64_t)first + (int64_t)strip * len;
+    at.cells = strip < strips ? (end - at.n0 < len ? (int32_t)(end - at.n0) : len) : 0;
+    return at;
 }
 
 constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u, kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
@@ -213,8 +318,8 @@ template <bool VEC, bool BIG>
 __global__ __launch_bounds__(kBlock, 5) void sample_counts_stream_kernel(
     const float* __restrict__ means, int32_t G, const CellInfo* __restrict__ cellinfo,
     const float* __restrict__ ga, const float* __restrict__ gbm1, const float* __restrict__ gphi,
-    int64_t N, uint32_t k0, uint32_t k1, int32_t* __restrict__ out, int64_t ld, int32_t strips,
-    int32_t strip_cells, uint2* __restrict__ heavy_list, uint32_t heavy_cap, uint2* __restrict__ heavy_dense,
+    int64_t N, uint32_t k0, uint32_t k1, int32_t* __restrict__ out, int64_t ld, StripPlan plan,
+    uint2* __restrict__ heavy_list, uint32_t heavy_cap, uint2* __restrict__ heavy_dense,
     const HeavyList* __restrict__ heavy_ptr)
 {
     // (K3h's lists are described by a record in device memory, read where it is needed -- in two rare branches and at the
@@ -253,20 +358,19 @@ __global__ __launch_bounds__(kBlock, 5) void sample_counts_stream_kernel(
     for (int k = tid - prnb::kTabShift; k < kInvTab + 2; k += kBlock) inv_k[k] = k > 0 ? 1.0f / (float)k : 0.0f;
     __syncthreads();
 
-    // block -> (gene tile, group of 4 strips); adjacent blocks share the gene tile (L2 reuse of
-    // the mean tensor's column slice and of the per-gene parameters)
-    const int32_t groups = (strips + 3) / 4;
-    const int32_t tile_g = blockIdx.x / groups;
-    const int32_t strip = (blockIdx.x - tile_g * groups) * 4 + wv;
-    const int32_t gbase = tile_g * kTileG;
-    const int32_t g0 = gbase + lane * 4;
-    const int64_t n0 = (int64_t)strip * strip_cells;
+    // block -> (class of the plan, gene tile, group of 4 strips): strip_of_region, on the scalar unit, once per wave (the
+    // plan is a kernel argument: scalar registers that nothing behind this point reads)
     const uint32_t region = blockIdx.x * 4u + (uint32_t)wv;
-    if (strip >= strips || n0 >= N) {                // whole wave leaves together (no barrier below)
+    // (the division's quotient comes out of the vector unit: said to be wave-uniform, as wv is)
+    const StripAt at = strip_of_region(plan, region);
+    const int32_t gbase = __builtin_amdgcn_readfirstlane(at.tile_g) * kTileG;
+    const int32_t g0 = gbase + lane * 4;
+    const int64_t n0 = (int64_t)__builtin_amdgcn_readfirstlane((int32_t)at.n0);      // (a cell index: under 2^31)
+    const int cells = __builtin_amdgcn_readfirstlane(at.cells);
+    if (cells <= 0) {                                // whole wave leaves together (no barrier below)
         if (lane == 0) heavy_late().count[region] = 0u;
         return;
     }
-    const int cells = (int)((N - n0 < strip_cells) ? (N - n0) : strip_cells);
 
     // lanes beyond G read some valid mean (see load_seg); a = b - 1 = 0 makes theta = 0, which
     // stage 2 drops before the class test

@@ -24,8 +24,9 @@
 // Host side, each decision in one place
 //   ScratchWord             the words of the ctx's device scratch
 //   Staging                 a call's arrays that may be host pointers (PROSSTT_AMD_HOST_INPUTS / _OUTPUT)
-//   stream_geometry         launch geometry and list capacities of a sample_counts call (PROSSTT_AMD_STRIP_CELLS, for
-//                           tests and tools, sets the strip length)
+//   stream_geometry         launch geometry (k3::strip_plan, the rule) and list capacities of a sample_counts call
+//                           (PROSSTT_AMD_STRIP_CELLS, _STRIP_TAPER and _STRIP_CLASSES, for tests and tools, set the bulk
+//                           strip length, the residency the short classes are sized by, and how many classes there are)
 //   stream_workspace        the regions of its workspace: their sizes and their addresses
 //   sampler_setup           the common front end of sample_counts and nb_params
 #include <hip/hip_runtime.h>
@@ -87,10 +88,11 @@ struct prosstt_amd_ctx {
     // the K3h list of the last sample_counts call (inside `ws`; read by prosstt_amd_last_list)
     k3::HeavyList list{};        // (list.seg_cnt == nullptr: none)
     uint64_t list_regions = 0;
-    int64_t list_groups = 0, list_strip_cells = 0;
+    k3::StripPlan list_plan{};
     const k3::CellInfo* list_info = nullptr;   // that call's cell records (N + 4 of them), for prosstt_amd_last_run_plan
     int64_t list_cells = 0;
     int heavy_grid = 1280;       // blocks of K3h that are resident at once on this device (5 per CU: its 30 496 B of LDS)
+    int stream_resident = 1280;  // ... and of the stream kernel (5 per CU: k3_stream.h), which its strip plan is sized by
     // domain check: one byte per row of the mean tensor last scanned ("has an entry that is not in (0, inf)"), and which tensor that was
     uint8_t* row_bad = nullptr;
     size_t row_bad_cap = 0;
@@ -189,8 +191,8 @@ struct Staging {
 
 // One launch prepares a sample_counts call: binary64 scaling/alpha/beta -> the binary32 sampler
 // parameters (and the zero-test factor), the per-cell records of the streaming kernel (k3::CellInfo;
-// N + 4 entries, the last cell repeated; skipped when `info` is NULL; `strip_cells`: the strip length of the launch they
-// are for, which their run words depend on), and the call's flag words.
+// N + 4 entries, the last cell repeated; skipped when `info` is NULL; `plan`: the strip plan of the launch they
+// are for, which their run words depend on -- a cell's strip length is that of its class), and the call's flag words.
 // With `row_bad` (a checked call) it is also the per-cell and per-gene part of the domain check: scipy's argument
 // check in the reference fails iff some mean m = M*s is not a positive finite number (zero, negative, infinite, NaN) or
 // some theta = a*m + b - 1 is < 0.  The first is decided factor by factor, so that no product can hide it: a scaling
@@ -207,7 +209,7 @@ __global__ void prep_kernel(const double* __restrict__ scaling, int64_t N,
                             const int64_t* __restrict__ cell_index,
                             uint32_t k0, uint32_t k1, k3::CellInfo* __restrict__ info, int64_t* __restrict__ flags,
                             const uint8_t* __restrict__ row_bad, uint32_t parity, k3::HeavyList heavy,
-                            k3::HeavyList* __restrict__ heavy_rec, int32_t strip_cells)
+                            k3::HeavyList* __restrict__ heavy_rec, k3::StripPlan plan)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (heavy_rec && i < k3::kSegs + 2) heavy.seg_cnt[i] = 0u;      // the fill of the dense lists K3h reads
@@ -245,12 +247,18 @@ __global__ void prep_kernel(const double* __restrict__ scaling, int64_t N,
         const float s_n = (float)scaling[n];
         asm volatile("" : "+v"(row_here), "+v"(row_before));
         const int64_t row = clamped(row_here);
-        // Where the cells of a strip share a row (k3::run_word, the rule; CellInfo::runs).  A strip length that divides 64
-        // puts every strip inside one wave of this kernel (a block is four whole waves, i = lane mod 64), and the words
+        // Where the cells of a strip share a row (k3::run_word, the rule; CellInfo::runs).  The classes of the plan start
+        // at multiples of 64 cells, so the cells of a wave of this kernel are of one class (a block is four whole waves,
+        // i = lane mod 64) and strip_cells is wave-uniform.  A strip length that divides 64
+        // puts every strip inside one wave of this kernel, and the words
         // come from two lane masks -- who starts a run, who is a cell -- with one more read of row_of_cell per thread:
         // reading on to the run's end, one dependent load after the other, costs a strip's worth of load latencies in a
         // kernel that is otherwise as long as its launch.
-        uint32_t word;
+        int32_t strip_cells = plan.c[0].strip_cells;
+#pragma unroll
+        for (int k = 1; k < k3::kPlanClasses; ++k)
+            if (k < plan.classes && n >= plan.c[k].first_cell) strip_cells = plan.c[k].strip_cells;
+        uint32_t word = 0u;
         if (strip_cells > 0 && 64 % strip_cells == 0) {               // (every thread of the wave comes by here)
             const uint32_t lane = threadIdx.x & 63u, pos = lane & (uint32_t)(strip_cells - 1), first = lane - pos;
             const bool cell_here = i < N;
@@ -261,8 +269,31 @@ __global__ void prep_kernel(const double* __restrict__ scaling, int64_t N,
             const unsigned long long behind = starts_m & ~((2ull << lane) - 1ull);      // the runs that start behind this lane
             const uint32_t end = behind ? (uint32_t)__ffsll((long long)behind) - 1u : first + (uint32_t)__popcll(cells_m);
             word = !cell_here ? 1u : (!starts_run ? 0u : ((end - lane) | (pos == 0u ? (uint32_t)__popcll(starts_m) << 16 : 0u)));
-        } else {
+        } else if (strip_cells != 2 * 64) {
             word = i < N + 4 ? k3::run_word(row_of_cell, i, N, rows, strip_cells) : 0u;
+        }
+        // A bulk class of 128-cell strips (always the first class: its strips start at multiples of 128, so a strip is waves
+        // 2j and 2j + 1 of a block, and it ends on a multiple of 128 or with N): every wave leaves its two masks in LDS, and
+        // the waves of the first class form their words from their own masks and their partner's.  (Every wave of the block
+        // comes by the barrier: the condition is the launch's.)
+        if (plan.c[0].strip_cells == 2 * 64) {
+            __shared__ unsigned long long masks[4][2];
+            const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, half = wave & 1u;
+            const bool cell_here = i < N;
+            const bool starts_run = cell_here && ((lane == 0u && half == 0u) || clamped(row_before) != row);
+            const unsigned long long starts_m = __builtin_amdgcn_ballot_w64(starts_run), cells_m = __builtin_amdgcn_ballot_w64(cell_here);
+            if (lane == 0u) { masks[wave][0] = starts_m; masks[wave][1] = cells_m; }
+            __syncthreads();
+            if (strip_cells == 2 * 64) {
+                const unsigned long long other_starts = masks[wave ^ 1u][0], other_cells = masks[wave ^ 1u][1];
+                const uint32_t pos = half * 64u + lane;
+                const uint32_t strip_end = (uint32_t)__popcll(cells_m) + (uint32_t)__popcll(other_cells);
+                const unsigned long long behind = starts_m & ~((2ull << lane) - 1ull);
+                const uint32_t end = behind ? half * 64u + (uint32_t)__ffsll((long long)behind) - 1u
+                                            : (half == 0u && other_starts ? 64u + (uint32_t)__ffsll((long long)other_starts) - 1u : strip_end);
+                const uint32_t runs = (uint32_t)__popcll(starts_m) + (uint32_t)__popcll(other_starts);
+                word = !cell_here ? 1u : (!starts_run ? 0u : ((end - pos) | (pos == 0u ? runs << 16 : 0u)));
+            }
         }
         if (i < N + 4) {
             k3::CellInfo c;
@@ -693,6 +724,7 @@ PA_EXPORT int prosstt_amd_ctx_create(int device, void* stream, prosstt_amd_ctx**
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k3::sample_counts_heavy_kernel, k3::kHeavyBlock, 0) == hipSuccess &&
         per_cu > 0 && prop.multiProcessorCount > 0)
         c->heavy_grid = per_cu * prop.multiProcessorCount;
+    if (prop.multiProcessorCount > 0) c->stream_resident = 5 * prop.multiProcessorCount;     // (__launch_bounds__(kBlock, 5) and its LDS)
     *out = c;
     return 0;
 }
@@ -750,32 +782,45 @@ struct SamplerArgs {
     k3::CellInfo* cellinfo;
 };
 
-// Geometry of a streaming-kernel launch (k3_stream.h): strips of 64 cells per wave (the kernel takes up
-// to 128; shorter ones when the problem is too small to give every SIMD of the chip a few waves), four
-// strips and one 256-gene tile per block.
+// Geometry of a streaming-kernel launch (k3_stream.h): the strip plan (k3::strip_plan: strips of 64 cells per wave, shorter
+// ones when the problem is too small to give every SIMD of the chip a few waves, and behind the bulk of a large launch a
+// few classes of ever shorter strips), four strips and one 256-gene tile per block.
 struct StreamGeometry {
-    int64_t tiles_g, strip_cells, strips, groups;
+    k3::StripPlan plan;
+    int64_t tiles_g, strip_cells, blocks;   // strip_cells: of the bulk class, the longest
     uint64_t regions;       // one region of the K3h list per wave
     uint32_t region_cap;    // room for one in 16 of a wave's samples (beyond that K3h redoes the region itself)
     uint32_t ent_cap;          // entries per segment of the dense lists K3h reads (k3::HeavyList)
 };
 
-static StreamGeometry stream_geometry(int64_t N, int32_t G)
+// for tests and tools: PROSSTT_AMD_STRIP_CELLS = 8, 16, 32 or 64 (the lengths the rule chooses from; anything else is
+// ignored) gives a small problem the strips of a large one -- alone, one uniform class, as ever --;
+// PROSSTT_AMD_STRIP_TAPER = R > 0 turns the graded plan on whatever the problem size, its short classes sized for R
+// resident blocks, and PROSSTT_AMD_STRIP_CELLS is then its bulk length (128 as well: what a large launch gets by the rule); PROSSTT_AMD_STRIP_CLASSES = 1 .. 4 bounds the number of classes
+static long env_number(const char* name)
+{
+    const char* v = getenv(name);
+    return v ? strtol(v, nullptr, 10) : 0;
+}
+
+static StreamGeometry stream_geometry(int64_t N, int32_t G, int resident)
 {
     StreamGeometry g;
-    g.tiles_g = ((int64_t)(G > 0 ? G : 0) + kTileG - 1) / kTileG;
-    g.strip_cells = k3::kStripCells / 2;    // 64: measured best on C3 (128: +1.7 %, 32: +2.7 %)
+    const long forced = env_number("PROSSTT_AMD_STRIP_CELLS"), taper = env_number("PROSSTT_AMD_STRIP_TAPER");
+    const long most = env_number("PROSSTT_AMD_STRIP_CLASSES");
+    const bool uniform = taper <= 0 && (forced == 8 || forced == 16 || forced == 32 || forced == 64);
+    g.plan = k3::strip_plan(N, G, uniform ? 0 : resident, (int32_t)(forced > 0 && forced <= k3::kStripCells ? forced : 0),
+                            (int32_t)(taper > 0 && taper <= 0x7fffffffl ? taper : 0), (int32_t)(most > 0 && most <= k3::kPlanClasses ? most : 0));
     const int64_t n = N > 0 ? N : 0;
-    while (g.strip_cells > 8 && ((n + g.strip_cells - 1) / g.strip_cells) * g.tiles_g < 4 * 5 * 1024) g.strip_cells /= 2;
-    // for tests and tools: a small problem with the strips of a large one (PROSSTT_AMD_STRIP_CELLS = 8, 16, 32 or 64, the
-    // lengths the rule above chooses from; anything else is ignored)
-    if (const char* forced = getenv("PROSSTT_AMD_STRIP_CELLS")) {
-        const long v = strtol(forced, nullptr, 10);
-        if (v == 8 || v == 16 || v == 32 || v == 64) g.strip_cells = v;
+    g.tiles_g = g.plan.tiles_g;
+    g.strip_cells = g.plan.c[0].strip_cells;
+    // (in 64 bits: a launch of 2^29 blocks or more is refused, and the plan's 32-bit block numbers are not used then)
+    g.blocks = 0;
+    for (int k = 0; k < g.plan.classes; ++k) {
+        const int64_t len = g.plan.c[k].strip_cells, cells = g.plan.c[k + 1].first_cell - g.plan.c[k].first_cell;
+        g.blocks += (((cells + len - 1) / len + 3) / 4) * g.tiles_g;
     }
-    g.strips = (n + g.strip_cells - 1) / g.strip_cells;
-    g.groups = (g.strips + 3) / 4;
-    g.regions = (uint64_t)(g.groups * g.tiles_g) * 4u;
+    g.regions = (uint64_t)g.blocks * 4u;
     g.region_cap = (uint32_t)g.strip_cells * (kTileG / 16);
     if (g.region_cap > 1024u) g.region_cap = 1024u;             // K3h's second phase takes kDense + 16 chunks of 64
     // the segments (what regions list beyond their first kDense entries) take one sample in 64 of the matrix between them
@@ -893,7 +938,7 @@ static int sampler_setup(prosstt_amd_ctx* c, Staging& st, const float* means, in
     prep_kernel<<<dim3((unsigned)((span + 255) / 256)), dim3(256), 0, c->stream>>>(
         scaling, N, alpha, beta, G, A->scal, A->ga, A->gbm1, A->gphi, row_of_cell, rows, cell_offset, cell_index,
         (uint32_t)seed, (uint32_t)(seed >> 32), A->cellinfo, geo ? c->scratch : nullptr,
-        row_bad, c->call_parity, A->heavy, A->heavy_rec, geo ? (int32_t)geo->strip_cells : 1);
+        row_bad, c->call_parity, A->heavy, A->heavy_rec, geo ? geo->plan : k3::strip_plan(N, G, 0, 0, 0, 0));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -964,11 +1009,48 @@ PA_EXPORT int prosstt_amd_last_run_plan(prosstt_amd_ctx* c, uint32_t* words, int
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *total = c->list_cells + 4;
-    if (strip_cells) *strip_cells = (int32_t)c->list_strip_cells;
+    if (strip_cells) *strip_cells = c->list_plan.c[0].strip_cells;
     const int64_t n = cap < *total ? cap : *total;
     if (n > 0)      // one word of every 32-byte record
         HIP_TRY(hipMemcpy2D(words, 4, (const char*)c->list_info + offsetof(k3::CellInfo, runs), sizeof(k3::CellInfo), 4, (size_t)n,
                             hipMemcpyDeviceToHost));
+    return 0;
+}
+PA_CATCH
+
+// classes[3 * k ..]: {first cell, strip length, first block} of class k
+static void plan_out(const k3::StripPlan& p, int32_t* classes, int32_t* n_classes, int32_t* tiles_g, int32_t* blocks)
+{
+    for (int k = 0; k < p.classes; ++k) {
+        classes[3 * k] = p.c[k].first_cell;
+        classes[3 * k + 1] = p.c[k].strip_cells;
+        classes[3 * k + 2] = p.c[k].first_block;
+    }
+    *n_classes = p.classes;
+    if (tiles_g) *tiles_g = p.tiles_g;
+    if (blocks) *blocks = p.c[p.classes].first_block;
+}
+
+PA_EXPORT int prosstt_amd_strip_plan(int64_t N, int32_t G, int32_t resident_blocks, int32_t strip_cells, int32_t taper,
+                                     int32_t* classes, int32_t* n_classes, int32_t* tiles_g, int32_t* blocks) try
+{
+    if (N < 0 || G < 0 || N > 0x7fffffffll || resident_blocks < 0 || taper < 0) return fail(PROSSTT_AMD_EINVAL, "bad size");
+    if (strip_cells != 0 && strip_cells != 8 && strip_cells != 16 && strip_cells != 32 && strip_cells != 64 && strip_cells != 128)
+        return fail(PROSSTT_AMD_EINVAL, "strip_cells is not 0, 8, 16, 32, 64 or 128");
+    if (!classes || !n_classes) return fail(PROSSTT_AMD_EINVAL, "NULL argument");
+    plan_out(k3::strip_plan(N, G, resident_blocks, strip_cells, taper, 0), classes, n_classes, tiles_g, blocks);
+    return 0;
+}
+PA_CATCH
+
+PA_EXPORT int prosstt_amd_last_strip_plan(prosstt_amd_ctx* c, int32_t* classes, int32_t* n_classes, int32_t* tiles_g, int32_t* blocks) try
+{
+    if (!c || !classes || !n_classes) return fail(PROSSTT_AMD_EINVAL, "NULL argument");
+    *n_classes = 0;
+    if (tiles_g) *tiles_g = 0;
+    if (blocks) *blocks = 0;
+    if (!c->list.seg_cnt) return 0;
+    plan_out(c->list_plan, classes, n_classes, tiles_g, blocks);
     return 0;
 }
 PA_CATCH
@@ -990,8 +1072,8 @@ PA_EXPORT int prosstt_amd_sample_counts(prosstt_amd_ctx* c, const float* means, 
         if (N > 0x7fffffffll) return fail(PROSSTT_AMD_EINVAL, "too many cells; chunk them");
         if ((uint64_t)(rows > 0 ? rows : 0) * (uint64_t)G >= ((uint64_t)1 << 61)) return fail(PROSSTT_AMD_EINVAL, "mean tensor too large");
     }
-    const StreamGeometry geo = stream_geometry(N, G);
-    if (geo.groups * geo.tiles_g > 0x1fffffffll) return fail(PROSSTT_AMD_EINVAL, "too many tiles; chunk the cells");
+    const StreamGeometry geo = stream_geometry(N, G, c ? c->stream_resident : 0);
+    if (geo.blocks > 0x1fffffffll) return fail(PROSSTT_AMD_EINVAL, "too many tiles; chunk the cells");
     int rc = sampler_setup(c, st, means, rows, G, row_of_cell, scaling, alpha, beta, N, flags, &A, &geo, cell_offset,
                            cell_index, seed);
     if (rc) return rc;
@@ -1010,7 +1092,7 @@ PA_EXPORT int prosstt_amd_sample_counts(prosstt_amd_ctx* c, const float* means, 
     if (flags & PROSSTT_AMD_TIME_KERNEL) {
         if ((rc = next_event_pair(c, &ev_start, &ev_stop))) return rc;
     }
-    const dim3 grid((unsigned)(geo.groups * geo.tiles_g)), block(k3::kBlock);
+    const dim3 grid((unsigned)geo.blocks), block(k3::kBlock);
     // full-length strips and more counts than the last-level cache (256 MB) takes: k3_stream.h, BIG
     const bool big = geo.strip_cells >= k3::kStripCells / 2 && (double)N * (double)ld_out * 4.0 >= 1073741824.0;
     // The dominant kernel is timed alone (PROSSTT_AMD_TIME_KERNEL): the two events ride on the kernel's OWN dispatch packet
@@ -1020,7 +1102,7 @@ PA_EXPORT int prosstt_amd_sample_counts(prosstt_amd_ctx* c, const float* means, 
 #define K3_LAUNCH(V, B)                                                                                          \
     hipExtLaunchKernelGGL((k3::sample_counts_stream_kernel<V, B>), grid, block, 0, c->stream, ev_start, ev_stop, 0,  \
         A.means, G, (const k3::CellInfo*)cellinfo, (const float*)A.ga, (const float*)A.gbm1, (const float*)A.gphi, N, k0, k1, \
-        d_out, ld_out, (int32_t)geo.strips, (int32_t)geo.strip_cells, heavy.list, heavy.cap, heavy.dense, (const k3::HeavyList*)A.heavy_rec)
+        d_out, ld_out, geo.plan, heavy.list, heavy.cap, heavy.dense, (const k3::HeavyList*)A.heavy_rec)
     if (vec && big) K3_LAUNCH(true, true);
     else if (vec) K3_LAUNCH(true, false);
     else if (big) K3_LAUNCH(false, true);
@@ -1033,7 +1115,7 @@ PA_EXPORT int prosstt_amd_sample_counts(prosstt_amd_ctx* c, const float* means, 
     const uint64_t region_blocks = (geo.regions + 15u) / 16u;
     const unsigned heavy_blocks = (unsigned)(region_blocks < 256u ? 256u : (region_blocks < (uint64_t)c->heavy_grid ? region_blocks : (uint64_t)c->heavy_grid));
     k3::sample_counts_heavy_kernel<<<dim3(heavy_blocks), dim3(k3::kHeavyBlock), 0, c->stream>>>(
-        (const k3::HeavyList*)A.heavy_rec, (uint32_t)geo.regions, (int32_t)geo.strips, (int32_t)geo.strip_cells, A.means, rows, G, A.row_of_cell,
+        (const k3::HeavyList*)A.heavy_rec, (uint32_t)geo.regions, geo.plan, A.means, rows, G, A.row_of_cell,
         A.scal, A.ga, A.gbm1, N, k0, k1, cell_offset, d_cell_index, d_out, ld_out,
         // the per-sample part of a checked call's domain test rides at the end of K3h (it leaves at once unless a gene has
         // alpha < 0 or beta < 1: prep_kernel's request word of this call's parity)
@@ -1042,8 +1124,7 @@ PA_EXPORT int prosstt_amd_sample_counts(prosstt_amd_ctx* c, const float* means, 
     HIP_TRY(hipGetLastError());
     c->list = heavy;
     c->list_regions = geo.regions;
-    c->list_groups = geo.groups;
-    c->list_strip_cells = geo.strip_cells;
+    c->list_plan = geo.plan;
     c->list_info = cellinfo;
     c->list_cells = N;
     c->call_parity ^= 1u;
@@ -1092,8 +1173,8 @@ PA_EXPORT int prosstt_amd_last_list(prosstt_amd_ctx* c, int64_t* cells, int32_t*
         if (nd + walks == 0 || written >= cap) continue;
         if (nd) HIP_TRY(hipMemcpy(dense, c->list.dense + r * k3::kDense, (size_t)nd * sizeof(uint2), hipMemcpyDeviceToHost));
         if (walks) HIP_TRY(hipMemcpy(wid, c->list.wid + r * k3::kWalkSlots, (size_t)walks * 4, hipMemcpyDeviceToHost));
-        const int64_t blk = (int64_t)(r >> 2), tile_g = blk / c->list_groups;
-        const int64_t n0 = ((blk - tile_g * c->list_groups) * 4 + (int64_t)(r & 3)) * c->list_strip_cells;
+        const k3::StripAt at = k3::strip_of_region(c->list_plan, (uint32_t)r);
+        const int64_t tile_g = at.tile_g, n0 = at.n0;
         for (uint32_t i = 0; i < nd + walks && written < cap; ++i, ++written) {
             const uint32_t pos = i < nd ? dense[i].x : (wid[i - nd] & 0xffffu);
             cells[written] = n0 + (pos >> 8);

@@ -196,6 +196,14 @@ class Context:
             self._h, words.ctypes.data_as(ctypes.c_void_p), words.size, ctypes.byref(total), ctypes.byref(strip)))
         return words, strip.value
 
+    def last_strip_plan(self):
+        """(classes, tiles_g, blocks): the strip plan of the last sample_counts call, as ``strip_plan`` gives it."""
+        classes = np.zeros((4, 3), np.int32)
+        n, tiles, blocks = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        _native.check(self._lib.prosstt_amd_last_strip_plan(
+            self._h, classes.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n), ctypes.byref(tiles), ctypes.byref(blocks)))
+        return classes[:n.value].copy(), tiles.value, blocks.value
+
     HW_OPS = dict(rcp=0, log2=1, exp2neg=2)
 
     def hw_math(self, op, first_bits, count):
@@ -384,6 +392,18 @@ def run_plan(row_of_cell, rows, strip_cells):
     _native.check(_native.load().prosstt_amd_run_plan(
         roc.ctypes.data_as(ctypes.c_void_p), roc.size, int(rows), int(strip_cells), words.ctypes.data_as(ctypes.c_void_p)))
     return words
+
+
+def strip_plan(n_cells, G, resident_blocks, strip_cells=0, taper=0):
+    """(classes, tiles_g, blocks): which cells the waves of the sampler's stream kernel take in a call of ``n_cells`` x
+    ``G`` on a device that holds ``resident_blocks`` of its blocks at once (prosstt_amd_strip_plan; no device work).
+    ``classes`` is an int32 array of up to 4 rows {first cell, strip length, first block}."""
+    classes = np.zeros((4, 3), np.int32)
+    n, tiles, blocks = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    _native.check(_native.load().prosstt_amd_strip_plan(
+        int(n_cells), int(G), int(resident_blocks), int(strip_cells), int(taper), classes.ctypes.data_as(ctypes.c_void_p),
+        ctypes.byref(n), ctypes.byref(tiles), ctypes.byref(blocks)))
+    return classes[:n.value].copy(), tiles.value, blocks.value
 
 
 def inverse_permutation(perm):

@@ -119,20 +119,15 @@ VARIANTS = {
     "bail3": [("constexpr int kBail = 6;", "constexpr int kBail = 3;")],
     "bail24": [("constexpr int kBail = 6;", "constexpr int kBail = 24;")],
     "bail32": [("constexpr int kBail = 6;", "constexpr int kBail = 32;")],
-    "strip128": [("    g.strip_cells = k3::kStripCells / 2;", "    g.strip_cells = k3::kStripCells;")],
-    # small problems (C2): a fixed strip length instead of halving down to 8 (real variants: any strip length is correct)
-    "smallstrip10": [("    while (g.strip_cells > 8 && ((n + g.strip_cells - 1) / g.strip_cells) * g.tiles_g < 4 * 5 * 1024) g.strip_cells /= 2;",
-                     "    if (((n + g.strip_cells - 1) / g.strip_cells) * g.tiles_g < 4 * 5 * 1024) g.strip_cells = 10;")],
-    "smallstrip12": [("    while (g.strip_cells > 8 && ((n + g.strip_cells - 1) / g.strip_cells) * g.tiles_g < 4 * 5 * 1024) g.strip_cells /= 2;",
-                     "    if (((n + g.strip_cells - 1) / g.strip_cells) * g.tiles_g < 4 * 5 * 1024) g.strip_cells = 12;")],
-    "smallstrip16": [("    while (g.strip_cells > 8 && ((n + g.strip_cells - 1) / g.strip_cells) * g.tiles_g < 4 * 5 * 1024) g.strip_cells /= 2;",
-                     "    if (((n + g.strip_cells - 1) / g.strip_cells) * g.tiles_g < 4 * 5 * 1024) g.strip_cells = 16;")],
-    "smallstrip20": [("    while (g.strip_cells > 8 && ((n + g.strip_cells - 1) / g.strip_cells) * g.tiles_g < 4 * 5 * 1024) g.strip_cells /= 2;",
-                     "    if (((n + g.strip_cells - 1) / g.strip_cells) * g.tiles_g < 4 * 5 * 1024) g.strip_cells = 20;")],
-    "smallstrip32": [("    while (g.strip_cells > 8 && ((n + g.strip_cells - 1) / g.strip_cells) * g.tiles_g < 4 * 5 * 1024) g.strip_cells /= 2;",
-                     "    if (((n + g.strip_cells - 1) / g.strip_cells) * g.tiles_g < 4 * 5 * 1024) g.strip_cells = 32;")],
+    "strip128": [("    int64_t L = 64;   ", "    int64_t L = 128;  ")],
+    # small problems (C2): a fixed strip length instead of halving down to 8 (real variants; k3::strip_plan's lengths are powers
+    # of two since round 18: the lengths 10, 12, 20, 24 and 40 that round 4 also measured cannot be built any more)
+    "smallstrip16": [("    while (L > 8 && ((n + L - 1) / L) * tiles < 4 * 5 * 1024) L /= 2;",
+                     "    if (((n + L - 1) / L) * tiles < 4 * 5 * 1024) L = 16;")],
+    "smallstrip32": [("    while (L > 8 && ((n + L - 1) / L) * tiles < 4 * 5 * 1024) L /= 2;",
+                     "    if (((n + L - 1) / L) * tiles < 4 * 5 * 1024) L = 32;")],
 
-    "strip32": [("    g.strip_cells = k3::kStripCells / 2;", "    g.strip_cells = k3::kStripCells / 4;")],
+    "strip32": [("    int64_t L = 64;   ", "    int64_t L = 32;   ")],
     # plain instead of non-temporal row stores
     "plainstore": [(STORE_2, "            __builtin_amdgcn_raw_buffer_store_b128(row4, out_rsrc, store_voff, flush_off, 0);")],
     # stage 3 waits for 48 / 40 entries (a deeper S2; the block's LDS still allows five per CU)
@@ -224,9 +219,6 @@ VARIANTS = {
         ("    const uint32_t region = blockIdx.x * 4u + (uint32_t)wv;", "    const uint32_t region = blk * 4u + (uint32_t)wv;"),
     ],
     # round 4 (real variants, for C2): strips of 20 / 24 / 12 cells -- one round of waves on the chip's 5120 wave slots
-    "strip20": [("    g.strips = (n + g.strip_cells - 1) / g.strip_cells;", "    g.strip_cells = 20;\n    g.strips = (n + g.strip_cells - 1) / g.strip_cells;")],
-    "strip24": [("    g.strips = (n + g.strip_cells - 1) / g.strip_cells;", "    g.strip_cells = 24;\n    g.strips = (n + g.strip_cells - 1) / g.strip_cells;")],
-    "strip12": [("    g.strips = (n + g.strip_cells - 1) / g.strip_cells;", "    g.strip_cells = 12;\n    g.strips = (n + g.strip_cells - 1) / g.strip_cells;")],
     # mean segments one cell ahead, requested at the END of a pass (one register rotation; the row store gets a whole pass before anything waits behind it)
     "pf1": [("        const Seg nn = load_seg(row2);\n        const uint64_t row3 = cinfo[3].row_bytes;",
              "        const uint64_t row3 = cinfo[3].row_bytes;"),
@@ -236,13 +228,8 @@ VARIANTS = {
     "svgpr": [SVGPR],
     "theta2": [THETA2],
     # C2 (5 000 x 5 000): strips of a fixed number of cells, whatever the problem size
-    "c2strip10": [("    g.strips = (n + g.strip_cells - 1) / g.strip_cells;", "    g.strip_cells = 10;\n    g.strips = (n + g.strip_cells - 1) / g.strip_cells;")],
-    "c2strip12": [("    g.strips = (n + g.strip_cells - 1) / g.strip_cells;", "    g.strip_cells = 12;\n    g.strips = (n + g.strip_cells - 1) / g.strip_cells;")],
-    "c2strip16": [("    g.strips = (n + g.strip_cells - 1) / g.strip_cells;", "    g.strip_cells = 16;\n    g.strips = (n + g.strip_cells - 1) / g.strip_cells;")],
-    "c2strip20": [("    g.strips = (n + g.strip_cells - 1) / g.strip_cells;", "    g.strip_cells = 20;\n    g.strips = (n + g.strip_cells - 1) / g.strip_cells;")],
-    "c2strip24": [("    g.strips = (n + g.strip_cells - 1) / g.strip_cells;", "    g.strip_cells = 24;\n    g.strips = (n + g.strip_cells - 1) / g.strip_cells;")],
-    "c2strip32": [("    g.strips = (n + g.strip_cells - 1) / g.strip_cells;", "    g.strip_cells = 32;\n    g.strips = (n + g.strip_cells - 1) / g.strip_cells;")],
-    "c2strip40": [("    g.strips = (n + g.strip_cells - 1) / g.strip_cells;", "    g.strip_cells = 40;\n    g.strips = (n + g.strip_cells - 1) / g.strip_cells;")],
+    "c2strip16": [("    while (L > 8 && ((n + L - 1) / L) * tiles < 4 * 5 * 1024) L /= 2;", "    L = 16;")],
+    "c2strip32": [("    while (L > 8 && ((n + L - 1) / L) * tiles < 4 * 5 * 1024) L /= 2;", "    L = 32;")],
     # one reciprocal for 1/u1 and 1/theta: r = rcp(u1 * th), 1/u1 = r * th, 1/th = r * u1 (a transcendental less, two multiplies more)
     "rcp1": [("    h.iu = hw_rcp(u1);\n    h.t2 = m * (hw_log2(u1) * hw_rcp(u1 - 1.0f));",
               "    const float th_ = u1 - 1.0f;\n    const float r_ = hw_rcp(u1 * th_);\n    h.iu = r_ * th_;\n    h.t2 = m * (hw_log2(u1) * (r_ * u1));")],

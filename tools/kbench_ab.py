@@ -1,6 +1,8 @@
 """A/B timing of the count sampler's dominant kernel over several builds of the library IN ONE PROCESS,
 rounds interleaved (variant 1, variant 2, ..., variant 1, ...): same device, same clock state, same inputs.
     python tools/kbench_ab.py [C3] [rounds] lib_a.so lib_b.so ...      ("shipped" = the in-tree library)
+A variant may carry environment settings that hold during its calls only, lib.so:NAME=VALUE,NAME=VALUE -- the strip plan's
+hooks (PROSSTT_AMD_STRIP_CELLS, _STRIP_TAPER, _STRIP_CLASSES), which the library reads at every call: one build, several plans.
 Prints per variant the median / min of the stream kernel's HIP-event time and of the whole call, and the
 sum of the counts (timing-only variants of tools/ablate.py give other sums: their outputs are wrong by
 construction)."""
@@ -14,6 +16,7 @@ cfg = args.pop(0) if args and args[0] in workloads.CONFIGS else "C3"
 rounds = int(args.pop(0)) if args and args[0].isdigit() else 12
 libs = args or ["shipped"]
 BURST = int(os.environ.get("KBENCH_BURST", "1"))
+HOOKS = ("PROSSTT_AMD_STRIP_CELLS", "PROSSTT_AMD_STRIP_TAPER", "PROSSTT_AMD_STRIP_CLASSES")
 ctx0 = device.get_context()
 w = workloads.build(cfg)
 pt, br, sc, rows = w.plan(int(os.environ["KBENCH_CELLS"]) if "KBENCH_CELLS" in os.environ else (125000 if cfg == "C5" else None))
@@ -28,8 +31,10 @@ vp, i32, i64, u32, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes
 
 
 class Variant:
-    def __init__(self, path):
-        self.name = os.path.basename(path)
+    def __init__(self, spec):
+        path, _, env = spec.partition(":")
+        self.env = dict(kv.split("=", 1) for kv in env.split(",") if kv)
+        self.name = os.path.basename(path) + (":" + env if env else "")
         self.lib = ctypes.CDLL(_native.LIBRARIES["sampler"].path if path == "shipped" else os.path.abspath(path))
         self.lib.prosstt_amd_ctx_create.argtypes = [ctypes.c_int, vp, ctypes.POINTER(vp)]
         self.lib.prosstt_amd_sample_counts.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, i64, u64, u64, vp, vp, i64, u32]
@@ -41,6 +46,9 @@ class Variant:
 
     def run(self, seed):
         # KBENCH_BURST=n: n calls back to back per round (the device keeps its clock), the call time is their mean
+        for name in HOOKS:
+            os.environ.pop(name, None)
+        os.environ.update(self.env)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(BURST):
