@@ -277,12 +277,7 @@ def _aggregate(L, level, c, always=False):
     ws = device.workspace("cluster", "prosstt_amd_cluster_workspace_bytes", dev, n, nnz)
     _native.check(L.prosstt_amd_cluster_aggregate_emit(st, _ptr(level.indptr), _ptr(level.indices), n, nnz, _ptr(cnew), n_new,
                                                        _ptr(ws), ws.numel(), _ptr(flags)), "cluster")
-    keys = ws[:8 * nnz].view(torch.int64)
-    sorted_keys, perm = torch.sort(keys, stable=True)
-    head = torch.ones(nnz, dtype=torch.int64, device=dev)
-    head[1:] = sorted_keys[1:] != sorted_keys[:-1]                      # 1 where a run of equal keys begins
-    pos = torch.cumsum(head, 0)
-    nnz_new = int(pos[-1].item())
+    sorted_keys, perm, pos, nnz_new = graph._sorted_runs(ws[:8 * nnz].view(torch.int64))
     indptr = torch.empty(n_new + 1, dtype=torch.int64, device=dev)
     indices = torch.empty(nnz_new, dtype=torch.int32, device=dev)
     u = torch.empty(nnz_new, dtype=torch.int64, device=dev)

@@ -3,8 +3,8 @@
 // strip_device.h (a lane's genes, its four counts of a row, the slab stores and fold); wave_reduce.h holds the wave sums.
 // Internal: included by every HIP library but the sampler (Makefile: the rows that list it), each a single translation
 // unit, and not installed under include/.  The libraries that read no count matrix (knn, graph, layout, tsne, dpt, cluster)
-// use the error plumbing, cdiv, pad, aligned and the two refusals only.  The strip kernels are those of stats, embed, hvg,
-// markers, ranks and trends.
+// use the error plumbing, cdiv, clamp64, pad, aligned and the two refusals only, and include graph_util.h after this file
+// for the refusals and grid rules they share.  The strip kernels are those of stats, embed, hvg, markers, ranks and trends.
 // The including file defines ABI_EINVAL and ABI_EHIP (its header's error codes) first.
 // (prosstt_amd.hip keeps macros of its own: its ABI has an ENOMEM code and reports e.what().)
 #pragma once

@@ -23,6 +23,7 @@
 #define ABI_EINVAL PROSSTT_AMD_CLUSTER_EINVAL
 #define ABI_EHIP PROSSTT_AMD_CLUSTER_EHIP
 #include "../abi_util.h"
+#include "../graph_util.h"                // check_workspace, stride_blocks
 #include "../wave_reduce.h"               // group_sum, wave_sum, wave_min
 
 #include <climits>
@@ -35,7 +36,6 @@ constexpr int kTableSlots = 1024;                    // of the LDS table: twice 
 constexpr int kTableRow = PROSSTT_AMD_CLUSTER_TABLE_ROW;
 constexpr int kRange = 2048;                         // community ids per pass of the range kernel
 constexpr int kFoldRun = 8;                          // sorted entries per thread of the fold
-constexpr int64_t kMaxBlocks = int64_t(1) << 20;     // of a grid-stride kernel
 constexpr uint32_t kBadGraph = PROSSTT_AMD_CLUSTER_BAD_GRAPH, kBadCommunity = PROSSTT_AMD_CLUSTER_BAD_COMMUNITY,
                    kBadBins = PROSSTT_AMD_CLUSTER_BAD_BINS;
 
@@ -46,12 +46,6 @@ int check_level(int64_t n, int64_t nnz)
     if (n < 1 || n >= (int64_t(1) << 31)) return fail(ABI_EINVAL, "need 1 <= n < 2^31 (got %lld)", (long long)n);
     if (nnz < 1 || nnz >= (int64_t(1) << 31)) return fail(ABI_EINVAL, "need 1 <= nnz < 2^31 (got %lld)", (long long)nnz);
     return 0;
-}
-
-unsigned stride_blocks(int64_t items)
-{
-    const int64_t b = cdiv(items, kThreads);
-    return (unsigned)(b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b));
 }
 
 // (begin, length) of row i, or an empty row and BAD_GRAPH
@@ -494,6 +488,7 @@ __global__ __launch_bounds__(kThreads) void cluster_fold_kernel(const int64_t* _
             const int64_t prior = p > 0 ? sorted[p - 1] : int64_t(-1);
             if (p == 0 || prior != key) {                                // the head of its run
                 indices[o] = (int32_t)(uint32_t)key;
+                // (the two indptr loops of sorted_runs.h's fold, written out: as shared functions they changed this kernel)
                 const int64_t row = key >> 32, prev = p > 0 ? prior >> 32 : int64_t(-1);
                 for (int64_t r = prev < -1 ? 0 : prev + 1; r <= row && r <= n_new; ++r) indptr[r] = o;
             }
@@ -601,10 +596,8 @@ ABI_EXPORT int prosstt_amd_cluster_aggregate_emit(void* stream, const int64_t* i
 {
     if (int rc = check_level(n, nnz)) return rc;
     if (n_new < 1 || n_new > n) return fail(ABI_EINVAL, "need 1 <= n_new <= n (got %lld)", (long long)n_new);
-    if (!indptr || !indices || !cnew || !ws || !status) return fail(ABI_EINVAL, "NULL argument");
-    if ((uintptr_t)ws % 16 != 0) return fail(ABI_EINVAL, "the workspace must be 16-byte aligned");
-    const size_t need = pad((size_t)nnz * 8);
-    if (ws_bytes < need) return workspace_too_small(ws_bytes, need);
+    if (!indptr || !indices || !cnew || !status) return fail(ABI_EINVAL, "NULL argument");
+    if (int rc = check_workspace(ws, ws_bytes, pad((size_t)nnz * 8))) return rc;
     cluster_emit_kernel<<<dim3((unsigned)cdiv(n, kThreads / kRowLanes)), dim3(kThreads), 0, (hipStream_t)stream>>>(
         indptr, indices, n, nnz, cnew, n_new, (int64_t*)ws, status);
     HIP_TRY(hipGetLastError());

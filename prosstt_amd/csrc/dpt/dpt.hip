@@ -14,6 +14,7 @@
 #define ABI_EINVAL PROSSTT_AMD_DPT_EINVAL
 #define ABI_EHIP PROSSTT_AMD_DPT_EHIP
 #include "../abi_util.h"
+#include "../graph_util.h"                // check_cells, default_slabs
 
 #include <cmath>
 
@@ -26,15 +27,12 @@ constexpr int kMaxSources = PROSSTT_AMD_DPT_MAX_SOURCES;
 constexpr int kRowsPerThread = 2;
 constexpr int kBlockRows = kThreads * kRowsPerThread;
 constexpr int kUnroll = 16;                    // columns of a group of the pair loop
-constexpr int kCUs = 256;                      // of the MI355X: the slabs' default fills them four times
 static_assert(kTile == kThreads, "a thread stages one column of a tile");
 static_assert(kBlockRows == PROSSTT_AMD_DPT_BLOCK_ROWS, "the header names the block's rows");
 
-bool cells_bad(int64_t N) { return N < 3 || N >= (int64_t(1) << 31); }
-
 int check_concordance(int64_t N, int32_t batch, int32_t slabs)
 {
-    if (cells_bad(N)) return fail(ABI_EINVAL, "need 3 <= N < 2^31 (got %lld)", (long long)N);
+    if (int rc = check_cells(N)) return rc;
     if (batch < 1 || batch > kMaxBatch) return fail(ABI_EINVAL, "need 1 <= batch <= %d (got %d)", kMaxBatch, (int)batch);
     if (slabs < 0 || slabs > kMaxSlabs) return fail(ABI_EINVAL, "need 0 <= slabs <= %d (got %d)", kMaxSlabs, (int)slabs);
     return 0;
@@ -52,7 +50,7 @@ Plan make_plan(int64_t N, int batch, int slabs)
     Plan p;
     const int64_t tiles = cdiv(N, kTile);
     p.row_blocks = cdiv(N, kBlockRows);
-    p.slabs = slabs ? slabs : (int)clamp64(cdiv(4 * kCUs, p.row_blocks * batch), 1, tiles < kMaxSlabs ? tiles : kMaxSlabs);
+    p.slabs = slabs ? slabs : default_slabs(p.row_blocks * batch, tiles, kMaxSlabs);
     p.tiles_per_slab = cdiv(tiles, p.slabs);
     p.bytes = pad((size_t)batch * (size_t)p.slabs * 2 * (size_t)N * 4);      // (lower, upper) int32 per pair, slab and row
     return p;
@@ -211,7 +209,7 @@ ABI_CATCH
 ABI_EXPORT int prosstt_amd_dpt_rows(void* stream, const double* vectors, int64_t row_stride, const double* weights, int64_t N,
                                     int64_t n_dcs, const int64_t* sources, int64_t n_sources, double* out) try
 {
-    if (cells_bad(N)) return fail(ABI_EINVAL, "need 3 <= N < 2^31 (got %lld)", (long long)N);
+    if (int rc = check_cells(N)) return rc;
     if (n_dcs < 1 || n_dcs >= N) return fail(ABI_EINVAL, "need 1 <= n_dcs < N (got %lld)", (long long)n_dcs);
     if (row_stride < n_dcs) return stride_below_row(row_stride, n_dcs);
     if (n_sources < 1 || n_sources > kMaxSources)
@@ -229,6 +227,7 @@ ABI_EXPORT int prosstt_amd_dpt_concordance(void* stream, const int32_t* ru, cons
                                            int32_t slabs, void* workspace, uint64_t bytes, int64_t* lower, int64_t* upper) try
 {
     if (int rc = check_concordance(N, batch, slabs)) return rc;
+    // (not graph_util.h's check_workspace: the alias refusal stands between the workspace's two, and their order stays)
     if (!ru || !rv || !workspace || !lower || !upper) return fail(ABI_EINVAL, "NULL argument");
     if ((uintptr_t)workspace % 16 != 0) return fail(ABI_EINVAL, "the workspace must be 16-byte aligned");
     if (lower == upper) return fail(ABI_EINVAL, "lower and upper must not alias each other");

@@ -6,8 +6,7 @@
 //                             lane c & 63, slot c >> 6: 16 slots, the unused ones +inf so that their exp is 0).  rho, the
 //                             mean and each of the 64 evaluations of f are wave reductions.  Checks the values.
 //   graph_emit_kernel         entry e = (i, r) becomes the keyed entries 2e and 2e + 1 of the workspace.
-//   graph_fold_kernel         one thread per sorted entry; the head of a run of equal keys folds it and writes the CSR
-//                             entry; the first head of a row writes indptr.
+//   graph_fold_kernel         sorted_runs.h's fold of the sorted entries into W: a run combines as (w + b) - w b.
 //   graph_normalize_kernel    16 lanes per row: <0> q = W 1; <1> K = W / (q_i q_j) into T and z = sqrt(K 1); <2> T = K /
 //                             (z_i z_j) in place.
 //   graph_spmv_kernel<G>      G lanes per row (4, 16, 64); lane s takes entries s, s + G, ..: a group's loads of columns
@@ -17,6 +16,8 @@
 #define ABI_EINVAL PROSSTT_AMD_GRAPH_EINVAL
 #define ABI_EHIP PROSSTT_AMD_GRAPH_EHIP
 #include "../abi_util.h"
+#include "../graph_util.h"                // the refusals and grid rules of the graph libraries, symmetrize_fold
+#include "../sorted_runs.h"               // fold_sorted_runs
 #include "../wave_reduce.h"               // group_sum, wave_sum, wave_min
 
 #include <cmath>
@@ -27,26 +28,6 @@ constexpr int kMaxK = 1024;
 constexpr int kSlots = kMaxK / 64;             // distances of a row per lane
 constexpr int kBisections = 64;
 constexpr int kNormLanes = 16;                 // lanes per row of the normalisation
-constexpr int64_t kMaxBlocks = int64_t(1) << 20;     // of a grid-stride kernel
-
-// 0, or the refusal of a bad size
-int check_sizes(int64_t N, int64_t k)
-{
-    if (N < 3 || N >= (int64_t(1) << 31)) return fail(ABI_EINVAL, "need 3 <= N < 2^31 (got %lld)", (long long)N);
-    const int64_t kmax = N - 1 < kMaxK ? N - 1 : kMaxK;
-    if (k < 2 || k > kmax) return fail(ABI_EINVAL, "need 2 <= k <= min(N - 1, %d) = %lld (got %lld)", kMaxK,
-                                       (long long)kmax, (long long)k);
-    return 0;
-}
-
-int check_csr(int64_t N, int64_t nnz)
-{
-    if (N < 3 || N >= (int64_t(1) << 31)) return fail(ABI_EINVAL, "need 3 <= N < 2^31 (got %lld)", (long long)N);
-    if (nnz < 0 || nnz > N * (N - 1)) return fail(ABI_EINVAL, "need 0 <= nnz <= N (N - 1) (got %lld)", (long long)nnz);
-    return 0;
-}
-
-size_t half_workspace(int64_t N, int64_t k) { return pad((size_t)(2 * N * k) * 8); }
 
 // -------------------------------------------------------------------------------------------------------- memberships
 
@@ -145,28 +126,9 @@ __global__ __launch_bounds__(kThreads) void graph_fold_kernel(const int64_t* __r
                                                               int64_t M, int64_t N, int64_t nnz, int64_t* __restrict__ indptr,
                                                               int32_t* __restrict__ indices, double* __restrict__ data)
 {
-    const int64_t stride = (int64_t)gridDim.x * kThreads;
-    for (int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x; p < M; p += stride) {
-        const int64_t key = sorted[p];
-        const int64_t before = p > 0 ? sorted[p - 1] : int64_t(-1);
-        if (p > 0 && before == key) continue;         // not the head of its run
-        const int64_t o = pos[p] - 1;
-        if (o < 0 || o >= nnz) continue;              // (a pos that is not the prefix sum of the heads: write nothing)
-        const uint64_t src = (uint64_t)perm[p];
-        double w = src < (uint64_t)M ? vals[src] : 0.0;
-        int64_t q = p + 1;
-        for (; q < M && sorted[q] == key; ++q) {
-            const uint64_t s = (uint64_t)perm[q];
-            const double b = s < (uint64_t)M ? vals[s] : 0.0;
-            w = (w + b) - w * b;
-        }
-        indices[o] = (int32_t)(uint32_t)key;
-        data[o] = w;
-        const int64_t row = key >> 32, prev = p > 0 ? before >> 32 : int64_t(-1);
-        for (int64_t r = prev < -1 ? 0 : prev + 1; r <= row && r <= N; ++r) indptr[r] = o;
-        if (q == M)                                   // the last run closes every row behind it
-            for (int64_t r = row < -1 ? 0 : row + 1; r <= N; ++r) indptr[r] = nnz;
-    }
+    fold_sorted_runs(
+        sorted, perm, pos, vals, M, N, nnz, indptr, indices, data, [](double w, double b) { return (w + b) - w * b; },
+        [](double w) { return w; });
 }
 
 // ------------------------------------------------------------------------------------------------------- normalisation
@@ -227,12 +189,6 @@ int choose_lanes(int64_t N, int64_t nnz)
     return nnz / N < 64 ? 16 : 64;
 }
 
-unsigned stride_blocks(int64_t items)
-{
-    const int64_t b = cdiv(items, kThreads);
-    return (unsigned)(b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b));
-}
-
 }  // namespace
 
 ABI_EXPORT const char* prosstt_amd_graph_last_error(void) { return g_err; }
@@ -240,7 +196,7 @@ ABI_EXPORT const char* prosstt_amd_graph_last_error(void) { return g_err; }
 ABI_EXPORT int prosstt_amd_graph_workspace_bytes(int64_t N, int64_t k, uint64_t* bytes) try
 {
     if (!bytes) return fail(ABI_EINVAL, "NULL argument");
-    if (int rc = check_sizes(N, k)) return rc;
+    if (int rc = check_sizes(N, k, kMaxK)) return rc;
     *bytes = 2 * half_workspace(N, k);
     return 0;
 }
@@ -249,10 +205,9 @@ ABI_CATCH
 ABI_EXPORT int prosstt_amd_graph_memberships(void* stream, const int32_t* index, const float* sqdist, int64_t N, int64_t k,
                                              double* a, double* rho, double* sigma, uint32_t* status) try
 {
-    if (int rc = check_sizes(N, k)) return rc;
+    if (int rc = check_sizes(N, k, kMaxK)) return rc;
     if (!index || !sqdist || !a || !rho || !sigma || !status) return fail(ABI_EINVAL, "NULL argument");
-    const unsigned blocks = (unsigned)cdiv(N, kThreads / 64);
-    graph_memberships_kernel<<<dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream>>>(
+    graph_memberships_kernel<<<dim3(wave_per_row_blocks(N)), dim3(kThreads), 0, (hipStream_t)stream>>>(
         index, sqdist, N, (int)k, std::log2((double)(k + 1)), a, rho, sigma, status);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -262,11 +217,10 @@ ABI_CATCH
 ABI_EXPORT int prosstt_amd_graph_symmetrize_emit(void* stream, const int32_t* index, const double* a, int64_t N, int64_t k,
                                                  void* ws, uint64_t ws_bytes) try
 {
-    if (int rc = check_sizes(N, k)) return rc;
-    if (!index || !a || !ws) return fail(ABI_EINVAL, "NULL argument");
-    if ((uintptr_t)ws % 16 != 0) return fail(ABI_EINVAL, "the workspace must be 16-byte aligned");
+    if (int rc = check_sizes(N, k, kMaxK)) return rc;
+    if (!index || !a) return fail(ABI_EINVAL, "NULL argument");
     const size_t half = half_workspace(N, k);
-    if (ws_bytes < 2 * half) return workspace_too_small(ws_bytes, 2 * half);
+    if (int rc = check_workspace(ws, ws_bytes, 2 * half)) return rc;
     graph_emit_kernel<<<dim3(stride_blocks(N * k)), dim3(kThreads), 0, (hipStream_t)stream>>>(
         index, a, N * k, k, (int64_t*)ws, (double*)((char*)ws + half));
     HIP_TRY(hipGetLastError());
@@ -278,17 +232,8 @@ ABI_EXPORT int prosstt_amd_graph_symmetrize_fold(void* stream, const int64_t* so
                                                  const int64_t* pos, int64_t N, int64_t k, int64_t nnz, const void* ws,
                                                  uint64_t ws_bytes, int64_t* indptr, int32_t* indices, double* data) try
 {
-    if (int rc = check_sizes(N, k)) return rc;
-    if (nnz < N * k || nnz > 2 * N * k)
-        return fail(ABI_EINVAL, "need N k <= nnz <= 2 N k (got %lld)", (long long)nnz);
-    if (!sorted_keys || !perm || !pos || !ws || !indptr || !indices || !data) return fail(ABI_EINVAL, "NULL argument");
-    if ((uintptr_t)ws % 16 != 0) return fail(ABI_EINVAL, "the workspace must be 16-byte aligned");
-    const size_t half = half_workspace(N, k);
-    if (ws_bytes < 2 * half) return workspace_too_small(ws_bytes, 2 * half);
-    graph_fold_kernel<<<dim3(stride_blocks(2 * N * k)), dim3(kThreads), 0, (hipStream_t)stream>>>(
-        sorted_keys, perm, pos, (const double*)((const char*)ws + half), 2 * N * k, N, nnz, indptr, indices, data);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return symmetrize_fold(graph_fold_kernel, kMaxK, stream, sorted_keys, perm, pos, N, k, nnz, ws, ws_bytes, indptr, indices,
+                           data);
 }
 ABI_CATCH
 

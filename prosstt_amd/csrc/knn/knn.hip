@@ -24,6 +24,7 @@
 #define ABI_EINVAL PROSSTT_AMD_KNN_EINVAL
 #define ABI_EHIP PROSSTT_AMD_KNN_EHIP
 #include "../abi_util.h"
+#include "../graph_util.h"                // check_workspace
 
 namespace {
 
@@ -315,9 +316,8 @@ ABI_EXPORT int prosstt_amd_knn_search(void* stream, const float* P, int64_t N, i
     Geometry g;
     if (int rc = geometry(N, d, k, chunk_rows, &g)) return rc;
     if (ld < d) return stride_below_row(ld, d);
-    if (!P || !index || !sqdist || !ws) return fail(PROSSTT_AMD_KNN_EINVAL, "NULL argument");
-    if ((uintptr_t)ws % 16 != 0) return fail(PROSSTT_AMD_KNN_EINVAL, "the workspace must be 16-byte aligned");
-    if (ws_bytes < g.bytes) return workspace_too_small(ws_bytes, g.bytes);
+    if (!P || !index || !sqdist) return fail(PROSSTT_AMD_KNN_EINVAL, "NULL argument");
+    if (int rc = check_workspace(ws, ws_bytes, g.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     float* slab = (float*)ws;
     const int64_t ctiles = g.np / kTile;

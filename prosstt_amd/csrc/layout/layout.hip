@@ -12,6 +12,7 @@
 #define ABI_EINVAL PROSSTT_AMD_LAYOUT_EINVAL
 #define ABI_EHIP PROSSTT_AMD_LAYOUT_EHIP
 #include "../abi_util.h"
+#include "../graph_util.h"                // check_csr, check_cells, stride_blocks
 #include "../wave_reduce.h"               // group_sum, wave_sum, wave_min
 
 #include <cmath>
@@ -20,7 +21,6 @@ namespace {
 
 constexpr int kMaxEpochs = 4096;
 constexpr int kMaxRate = 31;
-constexpr int64_t kMaxBlocks = int64_t(1) << 20;     // of the grid-stride probe
 #ifndef LAYOUT_UNROLL
 #define LAYOUT_UNROLL 4
 #endif
@@ -168,8 +168,6 @@ bool launch_epoch_lanes(int g, hipStream_t st, const int64_t* indptr, const int3
     }
 }
 
-bool cells_bad(int64_t N) { return N < 3 || N >= (int64_t(1) << 31); }
-
 }  // namespace
 
 ABI_EXPORT const char* prosstt_amd_layout_last_error(void) { return g_err; }
@@ -179,9 +177,7 @@ ABI_EXPORT int prosstt_amd_layout_epochs(void* stream, const int64_t* indptr, co
                                          int32_t n_epochs, double a, double b, double gamma, double alpha0,
                                          int32_t negative_sample_rate, uint64_t seed, int32_t lanes_per_row) try
 {
-    if (cells_bad(N)) return fail(ABI_EINVAL, "need 3 <= N < 2^31 (got %lld)", (long long)N);
-    if (nnz < 0 || nnz > N * (N - 1)) return fail(ABI_EINVAL, "need 0 <= nnz <= N (N - 1) (got %lld)", (long long)nnz);
-    if (c != 2 && c != 3) return fail(ABI_EINVAL, "need c = 2 or 3 (got %d)", (int)c);
+    if (int rc = check_csr(N, nnz, c)) return rc;
     if (n_epochs < 1 || n_epochs > kMaxEpochs) return fail(ABI_EINVAL, "need 1 <= n_epochs <= %d (got %d)", kMaxEpochs, (int)n_epochs);
     if (epoch_begin < 0 || epoch_begin > epoch_end || epoch_end > n_epochs)
         return fail(ABI_EINVAL, "need 0 <= epoch_begin <= epoch_end <= n_epochs (got %d, %d, %d)", (int)epoch_begin,
@@ -224,7 +220,7 @@ ABI_CATCH
 ABI_EXPORT int prosstt_amd_layout_negatives(void* stream, uint64_t seed, int32_t epoch, int64_t e_begin, int64_t count,
                                             int32_t rate, int64_t N, int32_t* out) try
 {
-    if (cells_bad(N)) return fail(ABI_EINVAL, "need 3 <= N < 2^31 (got %lld)", (long long)N);
+    if (int rc = check_cells(N)) return rc;
     if (epoch < 0 || epoch >= kMaxEpochs) return fail(ABI_EINVAL, "need 0 <= epoch < %d (got %d)", kMaxEpochs, (int)epoch);
     if (rate < 0 || rate > kMaxRate) return fail(ABI_EINVAL, "need 0 <= rate <= %d (got %d)", kMaxRate, (int)rate);
     if (e_begin < 0 || count < 0 || count > (int64_t(1) << 40) || e_begin > (int64_t(1) << 62))
@@ -233,9 +229,8 @@ ABI_EXPORT int prosstt_amd_layout_negatives(void* stream, uint64_t seed, int32_t
     if (!out) return fail(ABI_EINVAL, "NULL argument");
     const int64_t items = count * rate;
     if (items == 0) return 0;
-    const int64_t blocks = cdiv(items, kThreads);
-    layout_negatives_kernel<<<dim3((unsigned)(blocks > kMaxBlocks ? kMaxBlocks : blocks)), dim3(kThreads), 0,
-                              (hipStream_t)stream>>>(epoch_base(seed, epoch), e_begin, items, rate, N, out);
+    layout_negatives_kernel<<<dim3(stride_blocks(items)), dim3(kThreads), 0, (hipStream_t)stream>>>(
+        epoch_base(seed, epoch), e_begin, items, rate, N, out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

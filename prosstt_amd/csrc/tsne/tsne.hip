@@ -4,8 +4,7 @@
 //   tsne_affinities_kernel   one wave per row.  The row's k <= 1024 shifted distances stay in LDS, lane-strided (entry c is
 //                            lane c & 63's: kept in registers, the unrolled exp, log and division of 16 slots spilled
 //                            scalar registers).  Each of the 64 evaluations of H is two wave reductions.  Checks the values.
-//   tsne_fold_kernel         one thread per sorted entry; the head of a run of equal keys adds it up and writes the CSR
-//                            entry; the first head of a row writes indptr.
+//   tsne_fold_kernel         sorted_runs.h's fold of the sorted entries into P: a run adds up, and 2 N divides the sum.
 //   tsne_pair_kernel<C, ABS> the repulsion.  A block owns 512 rows (two per thread, 256 apart, so that two independent
 //                            chains are in flight) and one slab of column tiles.  A tile's positions go through LDS, and
 //                            every lane reads the same column at a time (a broadcast read).  Ten vector instructions per
@@ -19,6 +18,8 @@
 #define ABI_EINVAL PROSSTT_AMD_TSNE_EINVAL
 #define ABI_EHIP PROSSTT_AMD_TSNE_EHIP
 #include "../abi_util.h"
+#include "../graph_util.h"                // the refusals and grid rules of the graph libraries, symmetrize_fold
+#include "../sorted_runs.h"               // fold_sorted_runs
 #include "../wave_reduce.h"               // group_sum, wave_sum, wave_min
 
 #include <cmath>
@@ -31,32 +32,8 @@ constexpr int kTile = PROSSTT_AMD_TSNE_TILE;
 constexpr int kMaxSlabs = PROSSTT_AMD_TSNE_MAX_SLABS;
 constexpr int kRowsPerThread = 2;
 constexpr int kBlockRows = kThreads * kRowsPerThread;
-constexpr int kCUs = 256;                      // of the MI355X: the slabs' default fills them four times
 constexpr int kZBlocks = 256;                  // at most this many partial sums of Z
-constexpr int64_t kMaxBlocks = int64_t(1) << 20;     // of a grid-stride kernel
 constexpr int32_t kMaxIteration = 1 << 30;
-
-bool cells_bad(int64_t N) { return N < 3 || N >= (int64_t(1) << 31); }
-
-int check_sizes(int64_t N, int64_t k)
-{
-    if (cells_bad(N)) return fail(ABI_EINVAL, "need 3 <= N < 2^31 (got %lld)", (long long)N);
-    const int64_t kmax = N - 1 < kMaxK ? N - 1 : kMaxK;
-    if (k < 2 || k > kmax) return fail(ABI_EINVAL, "need 2 <= k <= min(N - 1, %d) = %lld (got %lld)", kMaxK,
-                                       (long long)kmax, (long long)k);
-    return 0;
-}
-
-int check_csr(int64_t N, int64_t nnz, int32_t c)
-{
-    if (cells_bad(N)) return fail(ABI_EINVAL, "need 3 <= N < 2^31 (got %lld)", (long long)N);
-    if (nnz < 0 || nnz > N * (N - 1)) return fail(ABI_EINVAL, "need 0 <= nnz <= N (N - 1) (got %lld)", (long long)nnz);
-    if (c != 2 && c != 3) return fail(ABI_EINVAL, "need c = 2 or 3 (got %d)", (int)c);
-    return 0;
-}
-
-// the half of the graph library's symmetrisation workspace: keys first, values behind them
-size_t half_workspace(int64_t N, int64_t k) { return pad((size_t)(2 * N * k) * 8); }
 
 // How the repulsion is cut and where its partial sums lie in the workspace.
 struct Plan {
@@ -72,7 +49,7 @@ Plan make_plan(int64_t N, int c, int slabs)
     Plan p;
     const int64_t tiles = cdiv(N, kTile);
     p.row_blocks = cdiv(N, kBlockRows);
-    p.slabs = slabs ? slabs : (int)clamp64(cdiv(4 * kCUs, p.row_blocks), 1, tiles < kMaxSlabs ? tiles : kMaxSlabs);
+    p.slabs = slabs ? slabs : default_slabs(p.row_blocks, tiles, kMaxSlabs);
     p.tiles_per_slab = cdiv(tiles, p.slabs);
     p.zblocks = (int)clamp64(cdiv(N, 4 * kThreads), 1, kZBlocks);
     p.zblock_rows = cdiv(cdiv(N, p.zblocks), kThreads) * kThreads;
@@ -151,28 +128,10 @@ __global__ __launch_bounds__(kThreads) void tsne_fold_kernel(const int64_t* __re
                                                              int64_t M, int64_t N, int64_t nnz, int64_t* __restrict__ indptr,
                                                              int32_t* __restrict__ indices, double* __restrict__ data)
 {
-    const int64_t stride = (int64_t)gridDim.x * kThreads;
     const double twice_n = 2.0 * (double)N;
-    for (int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x; p < M; p += stride) {
-        const int64_t key = sorted[p];
-        const int64_t before = p > 0 ? sorted[p - 1] : int64_t(-1);
-        if (p > 0 && before == key) continue;         // not the head of its run
-        const int64_t o = pos[p] - 1;
-        if (o < 0 || o >= nnz) continue;              // (a pos that is not the prefix sum of the heads: write nothing)
-        const uint64_t src = (uint64_t)perm[p];
-        double w = src < (uint64_t)M ? vals[src] : 0.0;
-        int64_t q = p + 1;
-        for (; q < M && sorted[q] == key; ++q) {
-            const uint64_t s = (uint64_t)perm[q];
-            w += s < (uint64_t)M ? vals[s] : 0.0;
-        }
-        indices[o] = (int32_t)(uint32_t)key;
-        data[o] = w / twice_n;
-        const int64_t row = key >> 32, prev = p > 0 ? before >> 32 : int64_t(-1);
-        for (int64_t r = prev < -1 ? 0 : prev + 1; r <= row && r <= N; ++r) indptr[r] = o;
-        if (q == M)                                   // the last run closes every row behind it
-            for (int64_t r = row < -1 ? 0 : row + 1; r <= N; ++r) indptr[r] = nnz;
-    }
+    fold_sorted_runs(
+        sorted, perm, pos, vals, M, N, nnz, indptr, indices, data, [](double w, double b) { return w + b; },
+        [twice_n](double w) { return w / twice_n; });
 }
 
 // -------------------------------------------------------------------------------------------------------- repulsion
@@ -380,24 +339,13 @@ __global__ __launch_bounds__(kThreads) void tsne_objective_kernel(const int64_t*
     if (lane == 0) rows[i] = acc;
 }
 
-unsigned stride_blocks(int64_t items)
-{
-    const int64_t b = cdiv(items, kThreads);
-    return (unsigned)(b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b));
-}
-
-unsigned wave_per_row_blocks(int64_t N) { return (unsigned)cdiv(N, kThreads / 64); }
-
 // the refusals that _gradient and _iterations share; the plan on success
 int check_descent(int64_t N, int64_t nnz, int32_t c, int32_t slabs, const void* ws, uint64_t ws_bytes, Plan& plan)
 {
     if (int rc = check_csr(N, nnz, c)) return rc;
     if (slabs < 0 || slabs > kMaxSlabs) return fail(ABI_EINVAL, "need 0 <= slabs <= %d (got %d)", kMaxSlabs, (int)slabs);
-    if (!ws) return fail(ABI_EINVAL, "NULL argument");
-    if ((uintptr_t)ws % 16 != 0) return fail(ABI_EINVAL, "the workspace must be 16-byte aligned");
     plan = make_plan(N, c, slabs);
-    if (ws_bytes < plan.bytes) return workspace_too_small(ws_bytes, plan.bytes);
-    return 0;
+    return check_workspace(ws, ws_bytes, plan.bytes);
 }
 
 bool positive_finite(double v) { return v > 0.0 && std::isfinite(v); }
@@ -469,7 +417,7 @@ ABI_CATCH
 ABI_EXPORT int prosstt_amd_tsne_affinities(void* stream, const int32_t* index, const float* sqdist, int64_t N, int64_t k,
                                            double perplexity, double* cond, double* beta, uint32_t* status) try
 {
-    if (int rc = check_sizes(N, k)) return rc;
+    if (int rc = check_sizes(N, k, kMaxK)) return rc;
     if (!(perplexity > 1.0) || !(perplexity < (double)k))
         return fail(ABI_EINVAL, "need 1 < perplexity < k = %lld (got %g)", (long long)k, perplexity);
     if (!index || !sqdist || !cond || !beta || !status) return fail(ABI_EINVAL, "NULL argument");
@@ -484,17 +432,8 @@ ABI_EXPORT int prosstt_amd_tsne_symmetrize_fold(void* stream, const int64_t* sor
                                                 const int64_t* pos, int64_t N, int64_t k, int64_t nnz, const void* ws,
                                                 uint64_t ws_bytes, int64_t* indptr, int32_t* indices, double* data) try
 {
-    if (int rc = check_sizes(N, k)) return rc;
-    if (nnz < N * k || nnz > 2 * N * k)
-        return fail(ABI_EINVAL, "need N k <= nnz <= 2 N k (got %lld)", (long long)nnz);
-    if (!sorted_keys || !perm || !pos || !ws || !indptr || !indices || !data) return fail(ABI_EINVAL, "NULL argument");
-    if ((uintptr_t)ws % 16 != 0) return fail(ABI_EINVAL, "the workspace must be 16-byte aligned");
-    const size_t half = half_workspace(N, k);
-    if (ws_bytes < 2 * half) return workspace_too_small(ws_bytes, 2 * half);
-    tsne_fold_kernel<<<dim3(stride_blocks(2 * N * k)), dim3(kThreads), 0, (hipStream_t)stream>>>(
-        sorted_keys, perm, pos, (const double*)((const char*)ws + half), 2 * N * k, N, nnz, indptr, indices, data);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return symmetrize_fold(tsne_fold_kernel, kMaxK, stream, sorted_keys, perm, pos, N, k, nnz, ws, ws_bytes, indptr, indices,
+                           data);
 }
 ABI_CATCH
 

@@ -213,6 +213,16 @@ def _raise_status(status):
 
 # ------------------------------------------------------------------------------------------------------ connectivities
 
+def _sorted_runs(keys):
+    """(sorted_keys, perm, pos, nnz) of the int64 device vector ``keys``, what a fold entry point reads: torch's stable
+    sort, ``pos`` the prefix sum of the heads of the runs of equal keys and ``nnz`` the number of runs (one host read)."""
+    sorted_keys, perm = _torch().sort(keys, stable=True)
+    head = _torch().ones_like(sorted_keys)
+    head[1:] = sorted_keys[1:] != sorted_keys[:-1]                      # 1 where a run of equal keys begins
+    pos = _torch().cumsum(head, 0)
+    return sorted_keys, perm, pos, int(pos[-1].item())
+
+
 def _symmetrize(L, idx, a, N, k, fold, fold_library):
     """(indptr, indices, data) of the symmetrisation of the directed values ``a`` (N, k) float64 on the entries ``idx``:
     the graph library's keyed emit, torch's sort and prefix sum, and ``fold``, an entry of library ``fold_library`` with
@@ -222,13 +232,7 @@ def _symmetrize(L, idx, a, N, k, fold, fold_library):
     st = device.current_stream(dev)
     ws = device.workspace("graph", "prosstt_amd_graph_workspace_bytes", dev, N, k)
     _native.check(L.prosstt_amd_graph_symmetrize_emit(st, _ptr(idx), _ptr(a), N, k, _ptr(ws), ws.numel()), "graph")
-    M = 2 * N * k
-    keys = ws[:8 * M].view(torch.int64)
-    sorted_keys, perm = torch.sort(keys, stable=True)
-    head = torch.ones(M, dtype=torch.int64, device=dev)
-    head[1:] = sorted_keys[1:] != sorted_keys[:-1]                      # 1 where a run of equal keys begins
-    pos = torch.cumsum(head, 0)
-    nnz = int(pos[-1].item())
+    sorted_keys, perm, pos, nnz = _sorted_runs(ws[:8 * 2 * N * k].view(torch.int64))
     indptr = torch.empty(N + 1, dtype=torch.int64, device=dev)
     indices = torch.empty(nnz, dtype=torch.int32, device=dev)
     data = torch.empty(nnz, dtype=torch.float64, device=dev)
