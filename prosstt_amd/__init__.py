@@ -41,6 +41,12 @@ densities from cells that have a branch and a pseudotime:
     tr = trends.expression_trends(X, sc, t, pt, br)   # tr.means (nodes, genes), tr.density, tr.to_tree()
     f = fit.count_model(X, sc, tr.labels, tr.means)   # f.alpha, f.beta
 
+Where every cell sits on the tree, for a matrix that does not come with its positions (the tree's own likelihood on the
+matrix cores):
+
+    from prosstt_amd import mapping
+    m = mapping.map_cells(X, sc, t)                   # m.node, m.branches, m.pseudotime, m.posterior, m.branch_posterior
+
 or, for unmodified scripts that say ``from prosstt import ...``:
 
     import prosstt_amd; prosstt_amd.install_as_prosstt()

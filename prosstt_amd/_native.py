@@ -194,6 +194,15 @@ LATER_LIBRARIES = {
         "prosstt_amd_trends_workspace_bytes": _int(i64, i64, i64, i64, _ptr_to(u64)),
         "prosstt_amd_trends_node_sums": _int(vp, vp, i64, i64, i64, vp, vp, vp, i64, i64, i64, vp, u64, vp, vp, vp),
     }, "prosstt_amd_trends_last_error"),
+    # mapping of cells onto the tree: the Poisson score of every cell at every node by f32 MFMA, its argmax and log-sum-exps
+    "mapping": _Library(_path("PROSSTT_AMD_MAPPING_LIB", "libprosstt_amd_mapping.so"), "prosstt_amd_mapping.h", True, {
+        "prosstt_amd_mapping_last_error": _text,
+        "prosstt_amd_mapping_workspace_bytes": _int(i64, i64, i64, i64, _ptr_to(u64)),
+        "prosstt_amd_mapping_node_scores": _int(vp, vp, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp, i64, i64, vp, u64, vp, vp,
+                                                vp, vp, vp, vp),
+        "prosstt_amd_mapping_node_scores_tiled": _int(vp, vp, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp, i64, i64, i32, vp, u64,
+                                                      vp, vp, vp, vp, vp, vp),
+    }, "prosstt_amd_mapping_last_error"),
 }
 
 
