@@ -47,6 +47,11 @@ matrix cores):
     from prosstt_amd import mapping
     m = mapping.map_cells(X, sc, t)                   # m.node, m.branches, m.pseudotime, m.posterior, m.branch_posterior
 
+The tree itself, for a matrix that comes without one (a regularised principal tree in PCA or diffusion-map space):
+
+    from prosstt_amd import ptree
+    lf = ptree.principal_tree(p.scores).to_tree(root=start_cell, G=X.shape[1])   # lf.tree, lf.branches, lf.pseudotime, lf.node
+
 or, for unmodified scripts that say ``from prosstt import ...``:
 
     import prosstt_amd; prosstt_amd.install_as_prosstt()

@@ -203,6 +203,13 @@ LATER_LIBRARIES = {
         "prosstt_amd_mapping_node_scores_tiled": _int(vp, vp, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp, i64, i64, i32, vp, u64,
                                                       vp, vp, vp, vp, vp, vp),
     }, "prosstt_amd_mapping_last_error"),
+    # principal tree: squared distances to the centres, the soft or hard assignment with its per-node sums, the projection
+    "ptree": _Library(_path("PROSSTT_AMD_PTREE_LIB", "libprosstt_amd_ptree.so"), "prosstt_amd_ptree.h", True, {
+        "prosstt_amd_ptree_last_error": _text,
+        "prosstt_amd_ptree_workspace_bytes": _int(i64, i64, i64, i32, _ptr_to(u64)),
+        "prosstt_amd_ptree_assign": _int(vp, vp, i64, i64, i64, vp, i64, i64, f64, vp, u64, vp, vp, vp, vp, vp, vp, vp),
+        "prosstt_amd_ptree_project": _int(vp, vp, i64, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp),
+    }, "prosstt_amd_ptree_last_error"),
 }
 
 

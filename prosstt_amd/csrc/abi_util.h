@@ -6,6 +6,7 @@
 // use the error plumbing, cdiv, clamp64, pad, aligned and the two refusals only, and include graph_util.h after this file
 // for the refusals and grid rules they share.  The strip kernels are those of stats, embed, hvg, markers, ranks and trends.
 // mapping reads the matrix through embed's matrix-core operand mapping and takes the plumbing and the refusals alone.
+// ptree reads float32 panels, not a count matrix, and takes the plumbing, cdiv, pad and the two refusals.
 // The including file defines ABI_EINVAL and ABI_EHIP (its header's error codes) first.
 // (prosstt_amd.hip keeps macros of its own: its ABI has an ENOMEM code and reports e.what().)
 #pragma once

@@ -1,5 +1,5 @@
 // Butterfly reductions over the lanes of a wave: every lane ends with the result of its group.
-// Internal: included by graph/graph.hip, layout/layout.hip, cluster/cluster.hip, tsne/tsne.hip and mapping/mapping.hip, not installed
+// Internal: included by graph/graph.hip, layout/layout.hip, cluster/cluster.hip, tsne/tsne.hip, mapping/mapping.hip and ptree/ptree.hip, not installed
 // under include/.
 // (What those libraries share besides is in graph_util.h, the host half, and sorted_runs.h, the fold; neither needs this file.)
 // The order is fixed, __shfl_xor with off = G / 2 down to 1: the binary64 and binary32 sums depend on it and the tests pin them
