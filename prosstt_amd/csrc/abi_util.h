@@ -5,7 +5,8 @@
 // unit, and not installed under include/.  The libraries that read no count matrix (knn, graph, layout, tsne, dpt, cluster)
 // use the error plumbing, cdiv, clamp64, pad, aligned and the two refusals only, and include graph_util.h after this file
 // for the refusals and grid rules they share.  The strip kernels are those of stats, embed, hvg, markers, ranks and trends.
-// mapping reads the matrix through embed's matrix-core operand mapping and takes the plumbing and the refusals alone.
+// embed's two products and mapping's pass multiply on the matrix cores: mfma_device.h holds their operand mapping, row load,
+// k-steps and tile map, and the host's choice of a <NT, VEC> instantiation; mapping takes the plumbing and the refusals besides.
 // ptree reads float32 panels, not a count matrix, and takes the plumbing, cdiv, pad and the two refusals.
 // The including file defines ABI_EINVAL and ABI_EHIP (its header's error codes) first.
 // (prosstt_amd.hip keeps macros of its own: its ABI has an ENOMEM code and reports e.what().)

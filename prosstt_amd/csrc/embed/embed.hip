@@ -3,20 +3,19 @@
 // Kernels (256 threads = 4 waves each; A[i][j] = log1p(X[i][j] * inv_size[i]) is formed in registers, never stored)
 //   embed_moments_kernel    a block owns a strip of 1024 genes over a range of rows; per gene the lane keeps S1 and S2 in
 //                           binary64 registers and stores them to slabs [row_blocks][G] at the end
-//   embed_matmul_kernel     Y = A.W: a block owns 128 rows (32 per wave) over one part of the genes, all l columns.  Per
-//                           step of 32 genes a lane loads 16 consecutive counts of its row (four 16-byte loads), the block
-//                           stages the 32 x l slice of W in LDS, and each wave runs 16 k-steps of v_mfma_f32_32x32x2_f32
-//                           per 32-column tile.  Partials go to a slab [parts][N][lp]
-//   embed_rmatmul_kernel    Z = A^T.Q: a block owns 256 genes (64 per wave: two per lane, one 8-byte load per row) over a
-//                           range of rows.  Per step of 32 rows the block stages the 32 x l slice of Q in LDS; each wave
-//                           runs 16 k-steps per (gene tile, column tile).  Partials go to a slab [row_blocks][G][lp]
+//   embed_matmul_kernel     Y = A.W, a matrix-core product (mfma_device.h: the operand mapping, the lane's 16 counts of a
+//                           step, the k-steps and the tile map): a block owns 128 rows (32 per wave) over one part of the
+//                           genes, all l columns, and stages the 32 x l slice of W of a step of 32 genes in LDS.  Partials
+//                           go to a slab [parts][N][lp]
+//   embed_rmatmul_kernel    Z = A^T.Q, the same product summed over the rows: a block owns 256 genes (64 per wave: two per
+//                           lane, one 8-byte load per row, so two accumulator sets) over a range of rows and stages the
+//                           32 x l slice of Q of a step of 32 rows in LDS.  Partials go to a slab [row_blocks][G][lp]
 //   embed_sum_panels_kernel / embed_sum_moments_kernel  sum a slab over its parts in ascending order
 // There are no floating-point atomics: the results do not depend on scheduling, and equal inputs give equal bits.
 //
-// The MFMA's k index is a permutation of the genes (matmul) or rows (rmatmul) of a step: in k-step s, lane half h
-// (lane >> 5) supplies index 16h + s of the step, for A and for the panel alike.  C/D map of a 32x32 tile: column
-// lane & 31, row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  lp = l rounded up to 32: the panel's extra columns and the
-// masked rows and genes of a step are zeros, so every l in 1..128 runs the same code.
+// What the products add to mfma_device.h: entry() forms A from the counts between the load and the k-steps, the summed
+// index is split into parts (matmul: genes, rmatmul: rows) whose partial tiles go to slabs, and lp = l rounded up to 32:
+// the panel's extra columns and the masked rows and genes of a step are zeros, so every l in 1..128 runs the same code.
 #include "../../../include/prosstt_amd_embed.h"
 
 #define ABI_EINVAL PROSSTT_AMD_EMBED_EINVAL
@@ -24,12 +23,10 @@
 #include "../abi_util.h"
 #include "../strip_device.h"              // the lane's genes, load_row4, for_lane_genes, fold_two_slabs
 #include "../log1p_entry.h"                 // entry(): the float32 log1p(x * inv), shared with markers/markers.hip
+#include "../mfma_device.h"                 // f32x16, kStep, load_row16, mfma_steps, tile_row, with_instantiation
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kStep = 32;                   // genes (matmul) or rows (rmatmul) per step of the k loop
 constexpr int kRowsMM = 128;                // matmul: rows per block, 32 per wave
 constexpr int kGenesRM = 256;               // rmatmul: genes per block, 64 per wave
 
@@ -63,11 +60,6 @@ Geometry geometry(int64_t N, int64_t G, int64_t l)
     g.bytes = g.m_bytes > g.mm_bytes ? g.m_bytes : g.mm_bytes;
     if (g.rm_bytes > g.bytes) g.bytes = g.rm_bytes;
     return g;
-}
-
-__device__ __forceinline__ f32x16 mfma(float a, float b, const f32x16& c)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------- moments
@@ -118,24 +110,6 @@ __global__ __launch_bounds__(kThreads) void embed_sum_moments_kernel(const doubl
 
 // ------------------------------------------------------------------------------------------------------------ A . W
 
-// The lane's 16 counts of one step: genes g0 + 16h .. g0 + 16h + 15 of its row (zeros outside the row or the part).
-template <bool VEC>
-__device__ __forceinline__ void load_row16(int32_t (&x)[16], const int32_t* __restrict__ rp, bool row_ok, int64_t g0,
-                                           int64_t ge, int h)
-{
-    const int64_t g = g0 + 16 * h;
-    if (VEC && row_ok && g0 + kStep <= ge) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int4 v = *reinterpret_cast<const int4*>(rp + g + 4 * q);
-            x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) x[q] = (row_ok && g + q < ge) ? rp[g + q] : 0;
-    }
-}
-
 // The thread's share of a 32 x lp panel slice: rows k0 .. k0 + 31 of P (row-major, l columns), zeros outside [k0, kend)
 // and in the columns l .. lp - 1.
 template <int NT>
@@ -154,7 +128,7 @@ __device__ __forceinline__ void load_panel(float (&p)[NT * 4], const float* __re
 template <int NT>
 __device__ __forceinline__ void stage_panel(float* sh, const float (&p)[NT * 4], int tid)
 {
-    constexpr int LP = NT * 32, LS = LP + 2;   // +2: the two lane halves read rows 16 apart, 32 banks apart
+    constexpr int LP = NT * 32, LS = slice_stride(NT);
 #pragma unroll
     for (int q = 0; q < NT * 4; ++q) {
         const int idx = tid + q * kThreads;
@@ -169,8 +143,8 @@ __global__ __launch_bounds__(kThreads) void embed_matmul_kernel(const int32_t* _
                                                                 int64_t genes_per_part, float* __restrict__ slab,
                                                                 uint32_t* __restrict__ status)
 {
-    constexpr int LP = NT * 32, LS = LP + 2;
-    __shared__ float wsh[kStep * LS];
+    constexpr int LP = NT * 32;
+    __shared__ float wsh[kStep * slice_stride(NT)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, c = lane & 31;
     const int64_t rbase = (int64_t)blockIdx.x * kRowsMM + wave * 32;
     const int64_t r = rbase + c;
@@ -201,19 +175,14 @@ __global__ __launch_bounds__(kThreads) void embed_matmul_kernel(const int32_t* _
             load_row16<VEC>(x, rp, row_ok, g0 + kStep, ge, h);
             load_panel<NT>(wp, W, l, g0 + kStep, ge, tid);
         }
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const float* b = wsh + (16 * h + s) * LS + c;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = mfma(a[s], b[32 * t], acc[t]);
-        }
+        mfma_steps<NT>(acc, a, wsh, h, c);
         __syncthreads();
     }
     if (neg < 0) atomicOr(status, 1u);
     float* out = slab + (size_t)blockIdx.y * (size_t)N * LP;
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-        const int64_t row = rbase + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+        const int64_t row = rbase + tile_row(reg, h);
         if (row < N) {
 #pragma unroll
             for (int t = 0; t < NT; ++t) out[row * LP + 32 * t + c] = acc[t][reg];
@@ -250,8 +219,8 @@ __global__ __launch_bounds__(kThreads) void embed_rmatmul_kernel(const int32_t* 
                                                                  int64_t rows_per_block, float* __restrict__ slab,
                                                                  uint32_t* __restrict__ status)
 {
-    constexpr int LP = NT * 32, LS = LP + 2;
-    __shared__ float qsh[kStep * LS];
+    constexpr int LP = NT * 32;
+    __shared__ float qsh[kStep * slice_stride(NT)];
     __shared__ float ish[kStep];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, c = lane & 31;
     const int64_t gwave = (int64_t)blockIdx.x * kGenesRM + wave * 64;
@@ -291,23 +260,14 @@ __global__ __launch_bounds__(kThreads) void embed_rmatmul_kernel(const int32_t* 
             load_panel<NT>(qp, Q, l, i1, r1, tid);
             if (tid < kStep) iv = (i1 + tid < r1) ? inv_size[i1 + tid] : 0.0f;
         }
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const float* b = qsh + (16 * h + s) * LS + c;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const float bv = b[32 * t];
-                acc[0][t] = mfma(a[s][0], bv, acc[0][t]);
-                acc[1][t] = mfma(a[s][1], bv, acc[1][t]);
-            }
-        }
+        mfma_steps<NT>(acc, a, qsh, h, c);
         __syncthreads();
     }
     if (neg < 0) atomicOr(status, 1u);
     float* out = slab + (size_t)blockIdx.y * (size_t)G * LP;
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-        const int64_t gi = gwave + 2 * ((reg & 3) + 8 * (reg >> 2) + 4 * h);   // tile row i is gene gwave + 2i + u
+        const int64_t gi = gwave + 2 * tile_row(reg, h);   // tile row i is gene gwave + 2i + u
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             if (gi + u < G) {
@@ -405,19 +365,10 @@ ABI_EXPORT int prosstt_amd_embed_matmul(void* stream, const int32_t* X, int64_t 
     hipStream_t st = (hipStream_t)stream;
     float* slab = (float*)ws;
     const dim3 grid((unsigned)cdiv(N, kRowsMM), (unsigned)geo.mm_parts);
-    const bool vec = aligned(X, ld, 4);
-#define PE_MM(NT)                                                                                                      \
-    (vec ? embed_matmul_kernel<NT, true><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, inv_size, W, l,               \
-                                                                          geo.mm_genes_per_part, slab, status)        \
-         : embed_matmul_kernel<NT, false><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, inv_size, W, l,              \
-                                                                           geo.mm_genes_per_part, slab, status))
-    switch (geo.lp / 32) {
-        case 1: PE_MM(1); break;
-        case 2: PE_MM(2); break;
-        case 3: PE_MM(3); break;
-        default: PE_MM(4); break;
-    }
-#undef PE_MM
+    with_instantiation(geo.lp / 32, aligned(X, ld, 4), [&](auto nt, auto vec) {
+        embed_matmul_kernel<nt(), vec()><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, inv_size, W, l, geo.mm_genes_per_part,
+                                                                          slab, status);
+    });
     HIP_TRY(hipGetLastError());
     return sum_panels(st, slab, geo.mm_parts, N, geo.lp, l, Y);
 }
@@ -435,19 +386,10 @@ ABI_EXPORT int prosstt_amd_embed_rmatmul(void* stream, const int32_t* X, int64_t
     hipStream_t st = (hipStream_t)stream;
     float* slab = (float*)ws;
     const dim3 grid((unsigned)cdiv(G, kGenesRM), (unsigned)geo.rm_row_blocks);
-    const bool vec = aligned(X, ld, 2);
-#define PE_RM(NT)                                                                                                      \
-    (vec ? embed_rmatmul_kernel<NT, true><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, inv_size, Q, l,              \
-                                                                           geo.rm_rows_per_block, slab, status)       \
-         : embed_rmatmul_kernel<NT, false><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, inv_size, Q, l,             \
-                                                                            geo.rm_rows_per_block, slab, status))
-    switch (geo.lp / 32) {
-        case 1: PE_RM(1); break;
-        case 2: PE_RM(2); break;
-        case 3: PE_RM(3); break;
-        default: PE_RM(4); break;
-    }
-#undef PE_RM
+    with_instantiation(geo.lp / 32, aligned(X, ld, 2), [&](auto nt, auto vec) {
+        embed_rmatmul_kernel<nt(), vec()><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, inv_size, Q, l, geo.rm_rows_per_block,
+                                                                           slab, status);
+    });
     HIP_TRY(hipGetLastError());
     return sum_panels(st, slab, geo.rm_row_blocks, G, geo.lp, l, Z);
 }

@@ -1,57 +1,29 @@
 // libprosstt_amd_mapping.so -- the score of every cell at every node of a lineage tree (include/prosstt_amd_mapping.h).
 //
 // Kernels (the definition is in the header)
-//   mapping_pass_kernel<NT, VEC>  embed_matmul_kernel's operand mapping over a node-major panel: a block owns 128 rows (32
-//                                 per wave) and 32 NT nodes and loops over all genes; the counts are converted in registers,
-//                                 the 32 x 32 NT panel slice is staged transposed in LDS, 16 k-steps of
-//                                 v_mfma_f32_32x32x2_f32 per 32-node tile; at a chain's end the binary32 accumulators are
-//                                 added into binary64 registers and cleared; the epilogue stores S = (D - s m) + c
+//   mapping_pass_kernel<NT, VEC>  a matrix-core product (mfma_device.h: the operand mapping, the lane's 16 counts of a step,
+//                                 the k-steps and the tile map) of the counts, converted in registers, with a node-major
+//                                 panel: a block owns 128 rows (32 per wave) and 32 NT nodes and loops over all genes; the
+//                                 32 x 32 NT panel slice of a step is read along the genes and staged transposed in LDS; at
+//                                 a chain's end the binary32 accumulators are added into binary64 registers and cleared;
+//                                 the epilogue stores S = (D - s m) + c
 //   mapping_finish_kernel         one wave per row of S: argmax, log-sum-exp, log-sum-exp of every branch
 // There is no floating-point atomic and every sum has a fixed order: equal inputs give equal bits.
-//
-// The MFMA's k index is a permutation of the genes of a step: in k-step s, lane half h (lane >> 5) supplies gene 16h + s of
-// the step, for the counts and for the panel alike.  C/D map of a 32x32 tile: column (node) lane & 31, row (cell)
-// (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  Masked rows, genes and nodes are zeros, so every shape runs the same code.
 #include "../../../include/prosstt_amd_mapping.h"
 
 #define ABI_EINVAL PROSSTT_AMD_MAPPING_EINVAL
 #define ABI_EHIP PROSSTT_AMD_MAPPING_EHIP
 #include "../abi_util.h"
+#include "../mfma_device.h"               // f32x16, kStep, load_row16, mfma, tile_row, with_instantiation
 #include "../wave_reduce.h"               // wave_sum: the butterfly of the log-sum-exp
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kStep = 32;                   // genes per step of the k loop
 constexpr int kRows = 128;                  // rows per block of the pass, 32 per wave
 constexpr int kFinishRows = kThreads / 64;  // rows per block of the finish kernel, one per wave
 constexpr int64_t kMaxNodes = PROSSTT_AMD_MAPPING_MAX_NODES;
 
-__device__ __forceinline__ f32x16 mfma(float a, float b, const f32x16& c)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
 // ------------------------------------------------------------------------------------------------------ the pass
-
-// The lane's 16 counts of one step: genes g0 + 16h .. g0 + 16h + 15 of its row (zeros outside the row or the matrix).
-template <bool VEC>
-__device__ __forceinline__ void load_row16(int32_t (&x)[16], const int32_t* __restrict__ rp, bool row_ok, int64_t g0,
-                                           int64_t G, int h)
-{
-    const int64_t g = g0 + 16 * h;
-    if (VEC && row_ok && g0 + kStep <= G) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int4 v = *reinterpret_cast<const int4*>(rp + g + 4 * q);
-            x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) x[q] = (row_ok && g + q < G) ? rp[g + q] : 0;
-    }
-}
 
 // The thread's share of the panel slice of a step: element idx = tid + 256 q is node n0 + idx / 32, gene g0 + idx % 32 (a
 // wave reads 128 consecutive bytes of two nodes); zeros past R and past G.
@@ -71,7 +43,7 @@ __device__ __forceinline__ void load_panel(float (&p)[NT * 4], const float* __re
 template <int NT>
 __device__ __forceinline__ void stage_panel(float* sh, const float (&p)[NT * 4], int tid)
 {
-    constexpr int LS = NT * 32 + 2;             // +2: the two lane halves read genes 16 apart, 32 banks apart
+    constexpr int LS = slice_stride(NT);
 #pragma unroll
     for (int q = 0; q < NT * 4; ++q) {
         const int idx = tid + q * kThreads;
@@ -87,8 +59,8 @@ __global__ __launch_bounds__(kThreads) void mapping_pass_kernel(const int32_t* _
                                                                 const double* __restrict__ constant, int steps_per_chain,
                                                                 double* __restrict__ S, uint32_t* __restrict__ status)
 {
-    constexpr int LP = NT * 32, LS = LP + 2;
-    __shared__ float psh[kStep * LS];
+    constexpr int LP = NT * 32;
+    __shared__ float psh[kStep * slice_stride(NT)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, c = lane & 31;
     const int64_t rbase = (int64_t)blockIdx.x * kRows + wave * 32;
     const int64_t r = rbase + c;
@@ -124,8 +96,8 @@ __global__ __launch_bounds__(kThreads) void mapping_pass_kernel(const int32_t* _
             load_panel<NT>(pp, P, ldp, R, G, n0, g0 + kStep, tid);
         }
 #pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const float* b = psh + (16 * h + s) * LS + c;
+        for (int s = 0; s < 16; ++s) {              // (mfma_device.h's mfma_steps, written out: as a call it changed this loop)
+            const float* b = psh + (16 * h + s) * slice_stride(NT) + c;
 #pragma unroll
             for (int t = 0; t < NT; ++t) acc[t] = mfma(a[s], b[32 * t], acc[t]);
         }
@@ -150,7 +122,7 @@ __global__ __launch_bounds__(kThreads) void mapping_pass_kernel(const int32_t* _
     }
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-        const int64_t row = rbase + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+        const int64_t row = rbase + tile_row(reg, h);
         if (row < N) {
             const double si = size[row];
 #pragma unroll
@@ -241,20 +213,6 @@ int check_sizes(int64_t N, int64_t G, int64_t R)
 
 size_t scores_bytes(int64_t N, int64_t R) { return pad((size_t)N * (size_t)R * 8); }
 
-template <int NT>
-void launch_pass(hipStream_t st, bool vec, const int32_t* X, int64_t N, int64_t G, int64_t ld, const double* s,
-                 const float* P, int64_t ldp, int64_t R, const double* m, const double* c, int steps_per_chain, double* S,
-                 uint32_t* status)
-{
-    const dim3 grid((unsigned)cdiv(N, kRows), (unsigned)cdiv(R, 32 * NT));
-    if (vec)
-        mapping_pass_kernel<NT, true><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, s, P, ldp, R, m, c, steps_per_chain, S,
-                                                                       status);
-    else
-        mapping_pass_kernel<NT, false><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, s, P, ldp, R, m, c, steps_per_chain, S,
-                                                                        status);
-}
-
 }  // namespace
 
 ABI_EXPORT const char* prosstt_amd_mapping_last_error(void) { return g_err; }
@@ -300,13 +258,10 @@ ABI_EXPORT int prosstt_amd_mapping_node_scores_tiled(void* stream, const int32_t
     // 13.1 and 15.3 at 50 000 x 20 000 x 400)
     const int nt = node_tile ? node_tile : (int)clamp64(cdiv(R, 32), 1, 2);
     const int steps = (int)(genes_per_chain / kStep);
-    const bool vec = aligned(X, ld, 4);
-    switch (nt) {
-    case 1: launch_pass<1>(st, vec, X, N, G, ld, s, P, ldp, R, m, c, steps, S, status); break;
-    case 2: launch_pass<2>(st, vec, X, N, G, ld, s, P, ldp, R, m, c, steps, S, status); break;
-    case 3: launch_pass<3>(st, vec, X, N, G, ld, s, P, ldp, R, m, c, steps, S, status); break;
-    default: launch_pass<4>(st, vec, X, N, G, ld, s, P, ldp, R, m, c, steps, S, status); break;
-    }
+    with_instantiation(nt, aligned(X, ld, 4), [&](auto tiles, auto vec) {
+        const dim3 grid((unsigned)cdiv(N, kRows), (unsigned)cdiv(R, 32 * tiles()));
+        mapping_pass_kernel<tiles(), vec()><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, s, P, ldp, R, m, c, steps, S, status);
+    });
     HIP_TRY(hipGetLastError());
     mapping_finish_kernel<<<dim3((unsigned)cdiv(N, kFinishRows)), dim3(kThreads), 0, st>>>(
         S, N, R, branch_offsets, B, best, best_score, lse, branch_lse, status);
