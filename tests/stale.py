@@ -8,8 +8,8 @@ bytes, where a fresh process, which gets zero pages from the allocator most of t
     0x7F   3.39e38 (float32), 1.38e306 (float64), 2139062143 (int32), 9187201950435737471 (int64)
 
 Out of reach: memory that native code allocates itself, tensors allocated before the block was entered, and allocations
-made inside torch's own operators (``x.clone()``, ``torch.zeros``: those are written in full by the operator).  A helper:
-nothing here is collected."""
+made inside torch's own operators (``x.clone()``, ``torch.zeros``: those are written in full by the operator).  What lies
+AROUND an allocation, a store or a load past its end, is tests/guard.py's.  A helper: nothing here is collected."""
 import contextlib
 
 import torch

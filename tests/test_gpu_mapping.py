@@ -251,16 +251,21 @@ def test_the_same_bits_twice_on_a_second_stream_without_scores_presented_and_for
     assert _bytes(mapping.node_scores(presented.in_plan_order(), s, P, m, c, offsets, scores=True)) == _bytes(base)
 
 
-def test_no_result_depends_on_stale_memory():
-    from test_gpu_stale_memory import _thrice
+def calls_mapping(place=lambda value: value):
+    """The library's label and its calls over ``_case``; ``place`` puts the device inputs (tests/test_gpu_stale_memory.py)."""
     from prosstt_amd import mapping
     X, s, P, m, c, offsets = _case()
-    shifted, aligned = _view(X, "shifted"), _view(X, "aligned")
-    _thrice("mapping", {
+    shifted, aligned = place(_view(X, "shifted")), place(_view(X, "aligned"))
+    return "mapping", {
         "node_scores": lambda: mapping.node_scores(shifted, s, P, m, c, offsets),
         "node_scores with scores, out='torch'": lambda: mapping.node_scores(aligned, s, P, m, c, offsets, scores=True,
                                                                              out="torch", genes_per_chain=32),
-    })
+    }
+
+
+def test_no_result_depends_on_stale_memory():
+    from test_gpu_stale_memory import _thrice
+    _thrice(*calls_mapping())
 
 
 # ------------------------------------------------------------------------------------------------------ ties

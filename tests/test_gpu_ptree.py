@@ -14,7 +14,8 @@ pytestmark = pytest.mark.gpu
 
 NS = (1, 63, 64, 65, 257, 1030)
 RS = (1, 2, 63, 64, 65, 130, 400)
-DS = (1, 2, 3, 15, 50, 128)
+DS = (1, 2, 3, 9, 15, 17, 32, 33, 50, 65, 128)      # every Q of ptree_sums_kernel<Q, HARD> and both sides of each boundary:
+#                                                    d = 1 .. 8 -> Q = 1, 9 .. 16 -> 2, 17 .. 32 -> 4, 33 .. 64 -> 8, 65 .. 128 -> 16
 LAYOUTS = ("aligned", "wide", "shifted")
 
 
@@ -132,7 +133,7 @@ def test_ties_go_to_the_lower_index_and_far_centres_underflow():
 
 # ------------------------------------------------------------------------------------------------------ the soft pass
 
-@pytest.mark.parametrize("d", (1, 3, 50, 128))
+@pytest.mark.parametrize("d", (1, 3, 17, 50, 128))
 def test_soft_pass_within_the_derived_bound(d):
     from prosstt_amd import ptree
     rng = np.random.default_rng(4200 + d)
@@ -161,6 +162,21 @@ def test_equal_distances_give_the_soft_sums_bit_for_bit(R):
     assert _same_bits(got.resp, want.resp) and _same_bits(got.gamma, want.gamma) and _same_bits(got.sums, want.sums)
     assert np.all(got.gamma == N / R)
     assert np.all(np.abs(got.free_energy - want.free_energy) <= pm.soft_bound(Y, C, 0.7, want)[0])
+
+
+@pytest.mark.parametrize("d", (8, 9, 17, 32, 33, 65))
+def test_equal_distances_give_the_soft_sums_bit_for_bit_for_every_q(d):
+    """The same for every ptree_sums_kernel<Q, false>: d = 8 -> Q = 1, 9 -> 2, 17 and 32 -> 4, 33 -> 8, 65 -> 16 (the hard pass
+    reaches every <Q, true> through DS above); two chunks of cells and a ragged one, two blocks of nodes; R is a power of two,
+    so that every product r * y is exact and the sums are IEEE in the header's order."""
+    from prosstt_amd import ptree
+    rng = np.random.default_rng(900 + d)
+    N, R = 300, 64
+    Y = rng.standard_normal((N, d)).astype(np.float32)
+    C = np.repeat(rng.standard_normal((1, d)).astype(np.float32), R, axis=0)
+    want, got = pm.assign(Y, C, 0.7), ptree.assign(_view(Y, "shifted"), C, 0.7, responsibilities=True)
+    assert np.all(got.resp == 1.0 / R) and not got.best.any()
+    assert _same_bits(got.resp, want.resp) and _same_bits(got.gamma, want.gamma) and _same_bits(got.sums, want.sums)
 
 
 # ------------------------------------------------------------------------------------------------------ the same bits
@@ -198,17 +214,31 @@ def test_same_bits_twice_on_a_second_stream_with_and_without_resp_and_for_device
     assert _bytes(q) == _bytes(p) == _bytes(ptree.project(Y, C, edges))
 
 
-def test_same_bits_over_stale_memory():
-    import stale
+def calls_ptree(place=lambda value: value):
+    """The library's label and its calls over ``_fixed_inputs``: the host arrays, and device views that ``place`` puts
+    (tests/test_gpu_stale_memory.py)."""
     from prosstt_amd import ptree
     Y, C = _fixed_inputs()
     edges = ptree.spanning_tree(C)
-    base = [_bytes(ptree.assign(Y, C, 0.0, responsibilities=True)), _bytes(ptree.assign(Y, C, 9.0, responsibilities=True)),
-            _bytes(ptree.project(Y, C, edges))]
+    Yv, Cv = place(_view(Y, "shifted")), place(_view(C, "wide"))
+    return "ptree", {
+        "assign, hard": lambda: ptree.assign(Y, C, 0.0, responsibilities=True),
+        "assign, soft": lambda: ptree.assign(Y, C, 9.0, responsibilities=True),
+        "project": lambda: ptree.project(Y, C, edges),
+        "assign, hard, device views": lambda: ptree.assign(Yv, Cv, 0.0, responsibilities=True, out="torch"),
+        "assign, soft, device views": lambda: ptree.assign(Yv, Cv, 9.0),
+        "project, device views": lambda: ptree.project(Yv, Cv, edges),
+    }
+
+
+def test_same_bits_over_stale_memory():
+    import stale
+    _, calls = calls_ptree()
+    base = [_bytes(call()) for call in calls.values()]
+    assert base[3] == base[0] and base[4] == base[1][:5] and base[5] == base[2]
     for byte in stale.BYTES:
         with stale.poisoned(byte) as state:
-            got = [_bytes(ptree.assign(Y, C, 0.0, responsibilities=True)),
-                   _bytes(ptree.assign(Y, C, 9.0, responsibilities=True)), _bytes(ptree.project(Y, C, edges))]
+            got = [_bytes(call()) for call in calls.values()]
         assert got == base and state.fills > 0, byte
 
 

@@ -103,11 +103,19 @@ def _cuda(array):
     return torch.from_numpy(np.array(array)).cuda()
 
 
-def _counts():
+def _identity(value):
+    """The placement of the inputs in this module: where their suites put them.  tests/test_gpu_guard_bands.py hands the
+    ``calls_*`` functions below (each returns its library's label and {name: a function without arguments}) a placement that
+    copies every device tensor of an input between guard bands (tests/guard.py); device tensors, and named tuples of them,
+    are what a placement is given."""
+    return value
+
+
+def _counts(place=_identity):
     """test_gpu_markers' draw at (259, 1025): five blocks of rows with a ragged last one, one whole strip of 1024 genes and
     a remainder; its shifted view (odd row stride, base off 16 bytes: the scalar loads), its aligned one, the size factors."""
     import test_gpu_markers as tm
-    return tm._view(259, 1025, "shifted"), tm._view(259, 1025, "aligned"), tm._host(259, 1025)[1]
+    return place(tm._view(259, 1025, "shifted")), place(tm._view(259, 1025, "aligned")), tm._host(259, 1025)[1]
 
 
 def test_the_comparison_sees_an_output_that_is_not_written():
@@ -133,7 +141,8 @@ def _skipped():
 
 # ------------------------------------------------------------------------------------------------------------ sampler
 
-def test_simulation_sample_density():
+def calls_sampler(place=_identity):
+    """(Every input is a host array or the tree: nothing to place.)"""
     from prosstt_amd import simulation as sim
     import test_gpu_fit
     tree = test_gpu_fit._tree()
@@ -147,35 +156,47 @@ def test_simulation_sample_density():
 
     calls = {"out=%s" % out: draw(out=out) for out in ("numpy", "numpy32", "numpy16", "csr", "torch")}
     calls["out=torch, order=plan"] = draw(out="torch", order="plan")
-    _thrice("simulation.sample_density", calls)
+    return "simulation.sample_density", calls
+
+
+def test_simulation_sample_density():
+    _thrice(*calls_sampler())
 
 
 # ------------------------------------------------------------------------------------------------- count-matrix readers
 
-def test_summary():
+def calls_summary(place=_identity):
     from prosstt_amd import summary
-    shifted, aligned, _ = _counts()
-    _thrice("summary.count_summary", {"shifted": lambda: summary.count_summary(shifted),
-                                      "aligned": lambda: summary.count_summary(aligned)})
+    shifted, aligned, _ = _counts(place)
+    return "summary.count_summary", {"shifted": lambda: summary.count_summary(shifted),
+                                     "aligned": lambda: summary.count_summary(aligned)}
 
 
-def test_embed():
+def test_summary():
+    _thrice(*calls_summary())
+
+
+def calls_embed(place=_identity):
     import torch
     from prosstt_amd import embed
-    shifted, aligned, s = _counts()
+    shifted, aligned, s = _counts(place)
     rng = np.random.default_rng(5)
-    W = torch.as_tensor(rng.standard_normal((1025, 50)).astype(np.float32)).cuda()
-    Q = torch.as_tensor(rng.standard_normal((259, 50)).astype(np.float32)).cuda()
+    W = place(torch.as_tensor(rng.standard_normal((1025, 50)).astype(np.float32)).cuda())
+    Q = place(torch.as_tensor(rng.standard_normal((259, 50)).astype(np.float32)).cuda())
     calls = {}
     for name, X in (("shifted", shifted), ("aligned", aligned)):
         calls["pca " + name] = lambda X=X: embed.pca(X, s, 20)
         calls["matmul " + name] = lambda X=X: embed.LogNormalized(X, s).matmul(W)
         calls["rmatmul " + name] = lambda X=X: embed.LogNormalized(X, s).rmatmul(Q)
         calls["gene_moments " + name] = lambda X=X: embed.LogNormalized(X, s).gene_moments()
-    _thrice("embed", calls)
+    return "embed", calls
 
 
-def test_hvg():
+def test_embed():
+    _thrice(*calls_embed())
+
+
+def calls_hvg(place=_identity):
     import torch
     import hvg_model
     import test_gpu_hvg
@@ -184,8 +205,8 @@ def test_hvg():
     D = torch.as_tensor(X).cuda()
     wide = torch.full((257, 1103), 7, dtype=torch.int32, device="cuda")
     wide[:, 1:1101] = D
-    view = wide[:, 1:1101]
-    _, gather = test_gpu_hvg._gather_matrix()                    # 67 x 1100, row stride 1103, a base off 16 bytes
+    D, view = place(D), place(wide[:, 1:1101])
+    gather = place(test_gpu_hvg._gather_matrix()[1])             # 67 x 1100, row stride 1103, a base off 16 bytes
     idx = np.random.default_rng(257).permutation(1100)[:257]
     calls = {}
     for name, M in (("aligned", D), ("shifted", view)):
@@ -193,15 +214,19 @@ def test_hvg():
         calls["seurat " + name] = lambda M=M: hvg.highly_variable_genes(M, sc, n_top, "seurat")
     calls["select_genes"] = lambda: hvg.select_genes(gather, idx)
     calls["select_genes, a mask"] = lambda: hvg.select_genes(gather, np.arange(1100) % 3 == 0)
-    _thrice("hvg", calls)
+    return "hvg", calls
 
 
-def test_markers():
+def test_hvg():
+    _thrice(*calls_hvg())
+
+
+def calls_markers(place=_identity):
     """``rank_genes_groups`` refuses a group of fewer than two cells (``markers.statistics``), so the empty group goes through
     ``group_moments``, the device pass of ``rank_genes_groups``, and the whole call gets three populated groups."""
     import test_gpu_markers as tm
     from prosstt_amd import markers
-    shifted, aligned, s = _counts()
+    shifted, aligned, s = _counts(place)
     sparse_labels = tm._labels(259, 3)                           # group 1 is empty, group 2 a single cell, some cells left out
     assert not (sparse_labels == 1).any() and (sparse_labels == 2).sum() == 1 and (sparse_labels == -1).any()
     labels = np.where(sparse_labels < 0, -1, np.arange(259) % 3)
@@ -213,10 +238,14 @@ def test_markers():
             X, s, sparse_labels, rows_per_block=64, out="torch")
     calls["rank_genes_groups wilcoxon"] = lambda: markers.rank_genes_groups(shifted[:, :130], s, labels, method="wilcoxon",
                                                                               tie_correct=True)
-    _thrice("markers", calls)
+    return "markers", calls
 
 
-def test_ranks():
+def test_markers():
+    _thrice(*calls_markers())
+
+
+def calls_ranks(place=_identity):
     import test_gpu_ranks as tr
     from prosstt_amd import ranks
     K, G = 3, 1024 + 37                                          # a whole strip of the emit kernel and its remainder
@@ -224,16 +253,20 @@ def test_ranks():
     s = tr._input("a", N, G)[1]
     calls = {}
     for view in tr.VIEWS:
-        X = tr._view("a", N, G, view)
+        X = place(tr._view("a", N, G, view))
         calls["two passes, " + view] = lambda X=X: ranks.rank_sums(X, s, labels, genes_per_pass=1024)
         calls["reference 0, out=torch, " + view] = lambda X=X: ranks.rank_sums(X, s, labels, reference=0, out="torch")
     labels2, N2 = tr._labels(1025, 7)                            # more than one tile of the sort
-    X2, s2 = tr._view("b", N2, 6, "shifted"), tr._input("b", N2, 6)[1]
+    X2, s2 = place(tr._view("b", N2, 6, "shifted")), tr._input("b", N2, 6)[1]
     calls["two sort tiles, tied keys"] = lambda: ranks.rank_sums(X2, s2, labels2)
-    _thrice("ranks.rank_sums", calls)
+    return "ranks.rank_sums", calls
 
 
-def test_fit():
+def test_ranks():
+    _thrice(*calls_ranks())
+
+
+def calls_fit(place=_identity):
     import test_gpu_fit as tf
     from prosstt_amd import fit
     calls = {}
@@ -241,13 +274,17 @@ def test_fit():
         rng = np.random.default_rng(257 * 100003 + 1025 * 7 + 3 + 31 * 9 + 7)
         _, view = tf._matrix(257, 1025, 3, "big", shift, rng)
         sc, labels, means, alpha, beta = tf._inputs(257, 1025, 7, 9, rng)
-        args = (view, sc, labels, means, alpha, beta)
+        args = (place(view), sc, labels, means, alpha, beta)
         calls["loglik, shift %d" % shift] = lambda args=args: fit.loglik(*args)
         calls["loglik, shift %d, out=torch" % shift] = lambda args=args: fit.loglik(*args, out="torch")
-    _thrice("fit.loglik", calls)
+    return "fit.loglik", calls
 
 
-def test_autocorr():
+def test_fit():
+    _thrice(*calls_fit())
+
+
+def calls_autocorr(place=_identity):
     import test_gpu_autocorr as ta
     import test_gpu_markers as tm
     from prosstt_amd import autocorr
@@ -255,106 +292,130 @@ def test_autocorr():
     s = tm._host(N, G)[1]
     calls = {}
     for kind in ta.GRAPHS:
-        g = ta._as_graph(ta._graph(N, kind))
+        g = place(ta._as_graph(ta._graph(N, kind)))
         for view in tm.VIEWS:
-            X = tm._view(N, G, view)
+            X = place(tm._view(N, G, view))
             tag = "%s graph, %s" % (kind, view)
             calls["graph_sums, " + tag] = lambda X=X, g=g: autocorr.graph_sums(X, s, g, rows_per_block=64, gene_tile=64)
             calls["graph_sums by default, out=torch, " + tag] = lambda X=X, g=g: autocorr.graph_sums(X, s, g, out="torch")
             calls["smooth, " + tag] = lambda X=X, g=g: autocorr.smooth(X, s, g, gene_tile=64)
             calls["smooth, unnormalised, out=numpy, " + tag] = lambda X=X, g=g: autocorr.smooth(X, s, g, normalize=False,
                                                                                                   out="numpy")
-    _thrice("autocorr", calls)
+    return "autocorr", calls
+
+
+def test_autocorr():
+    _thrice(*calls_autocorr())
 
 
 # -------------------------------------------------------------------------------------------------------- cell graphs
 
-def test_neighbors_knn():
+def calls_knn(place=_identity):
     import knn_model
     import test_gpu_knn as tk
     from prosstt_amd import neighbors
     host = knn_model.gaussian(257, 2, 1000 * 257 + 20 + 255)
     P = knn_model.gaussian(257, 31, 1000 * 257 + 310 + 256)
-    view = tk._input(P, (3, 1))                                  # rows that do not start on 16 bytes
-    lattice = tk._input(knn_model.lattice(2049, 7), (0, 0))      # ties across three segments of the select kernel
-    _thrice("neighbors.knn", {
+    view = place(tk._input(P, (3, 1)))                           # rows that do not start on 16 bytes
+    lattice = place(tk._input(knn_model.lattice(2049, 7), (0, 0)))      # ties across three segments of the select kernel
+    return "neighbors.knn", {
         "a host array, chunks of 100": lambda: neighbors.knn(host, 255, chunk_rows=100),
         "an unaligned view, chunks of 7": lambda: neighbors.knn(view, 256, chunk_rows=7, out="torch"),
-        "ties, chunks of 1000": lambda: neighbors.knn(lattice, 15, chunk_rows=1000)})
+        "ties, chunks of 1000": lambda: neighbors.knn(lattice, 15, chunk_rows=1000)}
 
 
-def test_graph():
+def test_neighbors_knn():
+    _thrice(*calls_knn())
+
+
+def calls_graph(place=_identity):
     import graph_model
     import test_gpu_graph as tg
     from prosstt_amd import graph
-    nb = tg._neighbors(graph_model.case(257, 65))                # rows longer than one group of 64 lanes
+    nb = place(tg._neighbors(graph_model.case(257, 65)))         # rows longer than one group of 64 lanes
     small = graph_model.case(300, 5)
-    nb_small = tg._neighbors(small)
-    g = graph.connectivities(nb, out="torch")
-    _thrice("graph", {
+    nb_small = place(tg._neighbors(small))
+    g = place(graph.connectivities(nb, out="torch"))
+    return "graph", {
         "connectivities, out=torch": lambda: graph.connectivities(nb, out="torch"),
         "connectivities of host arrays": lambda: graph.connectivities((np.array(small["idx"]), np.array(small["d2"]))),
         "transitions of connectivities": lambda: graph.transitions(g),
         "transitions of neighbours": lambda: graph.transitions(nb_small),
         "diffmap": lambda: graph.diffmap(nb_small, 15),
-        "diffmap, out=torch": lambda: graph.diffmap(nb, 5, out="torch")})
+        "diffmap, out=torch": lambda: graph.diffmap(nb, 5, out="torch")}
 
 
-def test_layout_optimize():
+def test_graph():
+    _thrice(*calls_graph())
+
+
+def calls_layout(place=_identity):
     import graph_model
     import layout_model
     import test_gpu_layout as tl
     from prosstt_amd import layout
     calls = {}
     for name, c in (((1000, 14), 2), ((257, 65), 3)):
-        conn = tl._conn_of(graph_model.case(*name)["W"])
-        Y = _cuda(np.random.default_rng(c).uniform(-10, 10, (name[0], c)).astype(np.float32))
+        conn = place(tl._conn_of(graph_model.case(*name)["W"]))
+        Y = place(_cuda(np.random.default_rng(c).uniform(-10, 10, (name[0], c)).astype(np.float32)))
         kw = dict(n_epochs=50, a=layout_model.A, b=layout_model.B, seed=3)
         for lanes in tl.LANES:
             calls["%s, c = %d, %d lanes" % (name, c, lanes)] = lambda conn=conn, Y=Y, kw=kw, lanes=lanes: layout.optimize(
                 conn, Y, 0, 3, lanes_per_row=lanes, **kw)
-    _thrice("layout.optimize", calls)
+    return "layout.optimize", calls
 
 
-def test_tsne():
+def test_layout_optimize():
+    _thrice(*calls_layout())
+
+
+def calls_tsne(place=_identity):
     import tsne_model
     import test_gpu_tsne as tt
     from prosstt_amd import tsne
     calls = {}
     for case, slab_counts in (((65, 63, 20.0), (3,)), ((300, 90, 30.0), (3, 0))):       # one tile: slabs 2 and 3 are empty
         cs = tsne_model.case(*case)
-        nb = tt._neighbors(cs["idx"], cs["d2"])
-        aff = tt._aff(case)
+        nb = place(tt._neighbors(cs["idx"], cs["d2"]))
+        aff = place(tt._aff(case))
         calls["affinities %s, out=torch" % (case,)] = lambda nb=nb, case=case: tsne.affinities(nb, case[2], out="torch")
         calls["affinities %s of host arrays" % (case,)] = lambda cs=cs, case=case: tsne.affinities(
             (np.array(cs["idx"]), np.array(cs["d2"])), case[2])
         for c in (2, 3):
-            Y = _cuda(tsne_model.pca_start(cs["P_panel"], c))
+            Y = place(_cuda(tsne_model.pca_start(cs["P_panel"], c)))
             for slabs in slab_counts:
                 tag = "%s, c = %d, slabs %d" % (case, c, slabs)
                 calls["gradient " + tag] = lambda aff=aff, Y=Y, slabs=slabs: tsne.gradient(aff, Y, exaggeration=12.0, slabs=slabs,
                                                                                          _sums=True)
                 calls["optimize " + tag] = lambda aff=aff, Y=Y, slabs=slabs: tsne.optimize(aff, Y, 0, 3, exploration=2,
                                                                                          learning_rate=50.0, slabs=slabs)
-    _thrice("tsne", calls)
+    return "tsne", calls
 
 
-def test_dpt():
+def test_tsne():
+    _thrice(*calls_tsne())
+
+
+def calls_dpt(place=_identity):
     import dpt_model
     import test_gpu_dpt as td
     from prosstt_amd import dpt
-    dm = td._device_run(300, 5)[0]
+    dm = place(td._device_run(300, 5)[0])
     root = dpt_model.truth(300, 5)[2]
-    _thrice("dpt.dpt", {
+    return "dpt.dpt", {
         "one branching, slabs 3": lambda: dpt.dpt(dm, root, n_branchings=1, slabs=3, _stages=True),
         "one branching, out=torch": lambda: dpt.dpt(dm, root, 15, n_branchings=1, min_group_size=40, out="torch"),
-        "no branching": lambda: dpt.dpt(dm, root)})
+        "no branching": lambda: dpt.dpt(dm, root)}
 
 
-def test_cluster_louvain():
+def test_dpt():
+    _thrice(*calls_dpt())
+
+
+def calls_cluster(place=_identity):
     import test_gpu_cluster as tc
     from prosstt_amd import _native, cluster
-    g = tc._connectivities(300, 5)
+    g = place(tc._connectivities(300, 5))                        # (host arrays: the wrapper moves them)
 
     def run(path):
         def call():
@@ -367,4 +428,8 @@ def test_cluster_louvain():
 
     calls = {"path %d" % path: run(path) for path in tc.PATHS}
     calls["out=torch"] = lambda: cluster.louvain(g, 2.0, out="torch")
-    _thrice("cluster.louvain", calls)
+    return "cluster.louvain", calls
+
+
+def test_cluster_louvain():
+    _thrice(*calls_cluster())

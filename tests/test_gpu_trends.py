@@ -258,24 +258,31 @@ def test_each_status_bit_alone_and_a_skipped_entry_leaves_the_rest_exact():
 
 # ----------------------------------------------------------------------------------------------------- stale memory
 
-def test_no_result_depends_on_stale_memory():
-    from test_gpu_stale_memory import _thrice
+def calls_trends(place=lambda value: value):
+    """The library's label and its calls over ``_case`` and ``_simulation``; ``place`` puts the device inputs
+    (tests/test_gpu_stale_memory.py)."""
     from prosstt_amd import trends
     X, csr, _ = _case()
-    shifted, aligned = _view(np.array(X), "shifted"), _view(np.array(X), "aligned")
+    shifted, aligned = place(_view(np.array(X), "shifted")), place(_view(np.array(X), "aligned"))
     w = _weights(csr, 161)
     t, Xs, pt, br, sc = _simulation()
+    part = place(Xs[:, :257])
 
     def whole():
-        tr = trends.expression_trends(Xs[:, :257], sc, t, pt, br, bandwidth=3.0)
+        tr = trends.expression_trends(part, sc, t, pt, br, bandwidth=3.0)
         return (tr.means, tr.variances, tr.density, tr.labels, tr.weight, tr.exposure, tr.effective_cells, tr.empty,
                 tr.sums.s1, tr.sums.s2_words)
 
-    _thrice("trends", {
+    return "trends", {
         "node_sums": lambda: trends.node_sums(shifted, w),
         "node_sums in chunks of 7, out='torch'": lambda: trends.node_sums(aligned, w, entries_per_block=7, out="torch"),
         "expression_trends": whole,
-    })
+    }
+
+
+def test_no_result_depends_on_stale_memory():
+    from test_gpu_stale_memory import _thrice
+    _thrice(*calls_trends())
 
 
 # ------------------------------------------------------------------------------------------------------ far offsets
