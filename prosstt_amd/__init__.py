@@ -52,6 +52,14 @@ The tree itself, for a matrix that comes without one (a regularised principal tr
     from prosstt_amd import ptree
     lf = ptree.principal_tree(p.scores).to_tree(root=start_cell, G=X.shape[1])   # lf.tree, lf.branches, lf.pseudotime, lf.node
 
+A question of the trends with an error bar: which genes change along the tree, which diverge after a fork (a per-gene
+regression of the counts on hat functions along the tree, under the count model's variance):
+
+    from prosstt_amd import regress
+    d = regress.tree_design(t, inner=1)
+    r = regress.regression(X, sc, m.node, d, alpha=f.alpha, beta=f.beta)   # r.coef, r.se, r.fitted()
+    r.wald(d.constant()).pvals_adj, r.wald(d.between("B", "C")).pvals_adj
+
 or, for unmodified scripts that say ``from prosstt import ...``:
 
     import prosstt_amd; prosstt_amd.install_as_prosstt()

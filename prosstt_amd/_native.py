@@ -1,6 +1,7 @@
 """
 ctypes binding of libprosstt_amd.so (include/prosstt_amd.h) and of the libraries beside it: each is described once in
-LIBRARIES, ADDED_LIBRARIES or LATER_LIBRARIES (the sampler's later entry points in SAMPLER_LATER), and load / check do the rest.
+LIBRARIES, ADDED_LIBRARIES, LATER_LIBRARIES or NEWER_LIBRARIES (the sampler's later entry points in SAMPLER_LATER), and load /
+check do the rest.
 
 There is NO CPU fallback: if the library is missing, or no gfx950 device is
 visible, every numeric entry point of the package raises.  torch is used only
@@ -212,6 +213,23 @@ LATER_LIBRARIES = {
     }, "prosstt_amd_ptree_last_error"),
 }
 
+# Every library added after tests/test_guard.py pinned the union of the three tables above to the rows of
+# tests/test_gpu_guard_bands.py (its census: one guard-band row per library, in a test file that no later change may edit)
+# goes HERE.  Rows of the same shape, looked up after the other three tables.  Every library in this table brings its own
+# guard-band test file (tests/test_gpu_<name>_guard_bands.py, on tests/guard.py as the shared file uses it);
+# tests/test_native_newer.py checks each row against its header, its makefile row and the built library, takes the symbol count
+# from the header, and checks that the four tables do not overlap and that each row's guard-band file is there.
+NEWER_LIBRARIES = {
+    # regression of the count model on a design: per gene the quasi-score, the information or the meat, and the
+    # quasi-log-likelihood, what regress.regression iterates on
+    "regress": _Library(_path("PROSSTT_AMD_REGRESS_LIB", "libprosstt_amd_regress.so"), "prosstt_amd_regress.h", True, {
+        "prosstt_amd_regress_last_error": _text,
+        "prosstt_amd_regress_workspace_bytes": _int(i64, i64, i64, _ptr_to(u64)),
+        "prosstt_amd_regress_normal_equations": _int(vp, vp, i64, i64, i64, vp, vp, i64, vp, i64, i64, vp, vp, vp, i32, i32, vp,
+                                                     u64, vp, vp, vp, vp, vp),
+    }, "prosstt_amd_regress_last_error"),
+}
+
 
 # Entry points of the sampler library declared after tests/test_native_libraries.py pinned its census of prosstt_amd.h:
 # (their header, symbol -> prototype), declared by ``load`` beside the sampler's row; tests/test_strip_plan_host.py checks
@@ -223,10 +241,10 @@ SAMPLER_LATER = ("prosstt_amd_plan.h", {
 
 
 def _library(name):
-    for table in (LIBRARIES, ADDED_LIBRARIES):
+    for table in (LIBRARIES, ADDED_LIBRARIES, LATER_LIBRARIES):
         if name in table:
             return table[name]
-    return LATER_LIBRARIES[name]
+    return NEWER_LIBRARIES[name]
 
 
 class NativeError(RuntimeError):
@@ -240,8 +258,8 @@ _lock = threading.Lock()
 
 
 def load(name="sampler"):
-    """The library ``name`` of LIBRARIES, ADDED_LIBRARIES or LATER_LIBRARIES with its prototypes declared (loaded once).  Raises if it has
-    not been built."""
+    """The library ``name`` of LIBRARIES, ADDED_LIBRARIES, LATER_LIBRARIES or NEWER_LIBRARIES with its prototypes declared (loaded
+    once).  Raises if it has not been built."""
     lib = _library(name)
     with _lock:
         if name not in _loaded:

@@ -1,0 +1,412 @@
+// libprosstt_amd_regress.so -- the quasi-score, the information (or the meat) and the quasi-log-likelihood of a per-gene
+// regression of a device count matrix on a design (include/prosstt_amd_regress.h holds the definition; DESIGN section 31
+// the reasons).
+//
+// Kernels (256 threads = 4 waves each)
+//   regress_pass_kernel  on fit_loglik_kernel's plan: a block owns a strip of 256 genes, a range of rows and ACC of the
+//                        p + p (p + 1) / 2 sums of (U, I) (blockIdx.z); a lane owns ONE gene, whose coefficients and sums
+//                        stay in registers across the rows.  Every block forms eta, mu, w and u of its entries itself,
+//                        by the same operations, so that the sums do not depend on ACC.  The instantiation ACC = 0 adds Q
+//                        and used and no sum of (U, I): log1p, log and their constants stay out of the other kernels'
+//                        registers.
+//                        What is uniform over the block is formed once per tile of kTile rows and read from LDS by every
+//                        lane at one address: the row's size factor and its logarithm, whether the row is used, its
+//                        design row, and for each of the block's sums its design factor (D_j for a sum of U, the rounded
+//                        product D_j D_k for one of I).  With ACC = 32 that is one factor per thread and tile.
+//                        <VEC = true>  rows that start on 16 bytes: the tile goes through LDS as in fit_loglik_kernel --
+//                                wave w loads rows w and w + 4, a lane 16 bytes (four genes) of each -- and every lane then
+//                                reads its own gene's column (a last strip of fewer than 256 genes: as <false>)
+//                        <VEC = false> any alignment: the lane loads its gene's entry of the row itself (4 bytes, coalesced)
+//   regress_finish_kernel  adds the blocks' partial sums in ascending block order
+// No atomics but the OR of a status bit.
+#include "../../../include/prosstt_amd_regress.h"
+
+#define ABI_EINVAL PROSSTT_AMD_REGRESS_EINVAL
+#define ABI_EHIP PROSSTT_AMD_REGRESS_EHIP
+#include "../abi_util.h"
+
+namespace {
+
+constexpr int kGenes = kThreads;            // genes per block: one per lane
+constexpr int kTile = 8;                    // rows of a tile: two 16-byte loads per lane in the aligned kernel
+constexpr int kMaxP = PROSSTT_AMD_REGRESS_MAX_P;
+constexpr int kMaxSums = kMaxP + kMaxP * (kMaxP + 1) / 2;      // 152
+constexpr double kLargest = 1e150;         // the largest size factor
+constexpr double kEtaMax = 700.0;
+constexpr double kBig = 1.7976931348623157e308;
+
+struct Geometry {
+    int64_t strips = 0, row_blocks = 0, rows_per_block = 0, sums = 0;
+    size_t slab = 0, used = 0;              // offsets of the slabs [row_blocks][sums + 1][G] (U, I, then Q) and [row_blocks][G]
+    size_t bytes = 0;
+};
+
+// The blocking of the rows depends on (N, strips) alone, never on p or the split (fit's rule).
+Geometry geometry(int64_t N, int64_t G, int64_t p)
+{
+    Geometry g;
+    g.strips = cdiv(G, kGenes);
+    g.sums = p + p * (p + 1) / 2;
+    const int64_t rb = clamp64(kTargetBlocks / g.strips, 1, cdiv(N, kStripMinRows));
+    g.rows_per_block = cdiv(N, rb);
+    g.row_blocks = cdiv(N, g.rows_per_block);
+    const size_t cells = (size_t)g.row_blocks * (size_t)G;
+    g.slab = 0;
+    g.used = g.slab + pad(cells * (size_t)(g.sums + 1) * 8);
+    g.bytes = g.used + pad(cells * 4);
+    return g;
+}
+
+// Finite with a >= 0 and b >= 1 (false for a NaN).
+__device__ __forceinline__ bool admissible(double a, double b) { return a >= 0.0 && a <= kBig && b >= 1.0 && b <= kBig; }
+
+template <bool VEC, int ACC>
+__global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* __restrict__ X, int64_t N, int64_t G, int64_t ld,
+                                                                const double* __restrict__ size,
+                                                                const int32_t* __restrict__ labels, int32_t K,
+                                                                const double* __restrict__ design, int64_t ldd, int32_t p,
+                                                                const double* __restrict__ coef,
+                                                                const double* __restrict__ alpha,
+                                                                const double* __restrict__ beta, int32_t meat,
+                                                                int64_t rows_per_block, double* __restrict__ slab,
+                                                                uint32_t* __restrict__ usedslab, uint32_t* __restrict__ status)
+{
+    constexpr bool QPASS = ACC == 0;                      // this instantiation adds Q and used, and no sum of (U, I)
+    constexpr int SLOTS = QPASS ? 1 : ACC;
+    static_assert(kThreads % SLOTS == 0 && kTile * SLOTS <= kThreads, "a thread forms at most one factor of a tile, of one sum");
+    __shared__ int32_t tile[VEC ? kTile : 1][kGenes];
+    __shared__ double s_size[kTile], s_logs[kTile];
+    __shared__ int32_t s_use[kTile];
+    __shared__ double s_design[kTile][kMaxP];
+    __shared__ double s_factor[kTile][SLOTS], s_second[kTile][SLOTS];
+    const int tid = threadIdx.x;
+    const int64_t gbase = (int64_t)blockIdx.x * kGenes;
+    const int64_t g = gbase + tid;
+    const bool mine = g < G;
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
+    const int64_t r1 = (r0 + rows_per_block < N) ? r0 + rows_per_block : N;
+    const int sums = p + p * (p + 1) / 2;
+    const int a0 = (int)blockIdx.z * ACC;                 // the block's first sum
+    const int na = QPASS ? 0 : ((sums - a0 < ACC) ? sums - a0 : ACC);      // how many it has
+    const int nu = (p - a0 < 0) ? 0 : ((p - a0 < na) ? p - a0 : na);      // how many of them are sums of U (the first ones)
+    const bool mixed = nu > 0 && nu < na;                 // sums of U and of I: two factors per sum, one of them 0
+    const bool staged = VEC && gbase + kGenes <= G;       // (the last, partial strip reads as the unaligned kernel does)
+
+    // The gene's parameters and coefficients are judged HERE, before any arithmetic on them (the header's rule).
+    uint32_t flags = 0;
+    double a = 0.0, b = 2.0;
+    double c[kMaxP], acc[SLOTS];
+    if (mine) {
+        const double av = alpha[g], bv = beta[g];
+        if (admissible(av, bv)) {
+            a = av;
+            b = bv;
+        } else {
+            flags |= PROSSTT_AMD_REGRESS_PARAMETER;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kMaxP; ++j) {
+        c[j] = 0.0;
+        if (mine && j < p) {
+            const double cv = coef[(int64_t)j * G + g];
+            if (__builtin_fabs(cv) <= kBig)
+                c[j] = cv;
+            else
+                flags |= PROSSTT_AMD_REGRESS_COEFFICIENT;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < SLOTS; ++i) acc[i] = 0.0;
+    double logb = 0.0;
+    if constexpr (QPASS) logb = log(b);
+    double q = 0.0;
+    uint32_t used = 0;
+    int32_t neg = 0;
+
+    // the sum whose factors this thread forms for the tiles (thread tid: row tid / ACC of the tile, sum a0 + tid % ACC):
+    // fj == fk for a sum of U (the factor is D[fj]), fj <= fk for one of I (D[fj] D[fk]), fj < 0 beyond the last sum
+    const int frow = tid / SLOTS, fslot = tid % SLOTS;
+    int fj = -1, fk = -1;
+    bool fpair = false;
+    if (frow < kTile && fslot < na) {
+        const int s = a0 + fslot;
+        if (s < p) {
+            fj = fk = s;
+        } else {
+            int t = s - p, j = 0;
+            while (t >= p - j) {
+                t -= p - j;
+                ++j;
+            }
+            fj = j;
+            fk = j + t;
+            fpair = true;
+        }
+    }
+
+    // where the lane's sums go, formed here so that the loop need not keep the kernel's arguments for it (fit's device: in
+    // vector registers from here on; kept as scalar arguments, some of them spill)
+    const size_t gat = (size_t)(mine ? g : 0);
+    double* sums_out = slab + ((size_t)blockIdx.y * (size_t)(sums + 1) + (size_t)a0) * (size_t)G + gat;
+    double* q_out = slab + ((size_t)blockIdx.y * (size_t)(sums + 1) + (size_t)sums) * (size_t)G + gat;
+    uint32_t* used_out = usedslab + (size_t)blockIdx.y * (size_t)G + gat;
+    uint32_t* status_out = status;
+    size_t out_stride = (size_t)G;
+    asm volatile("" : "+v"(sums_out), "+v"(q_out), "+v"(used_out), "+v"(status_out), "+v"(out_stride));
+
+    // the lane's part of a tile's loads: row (wave + 4 i) of the tile, genes 4 * (lane of the wave) .. + 3 of the strip
+    const int lrow = tid >> 6, lcol = 4 * (tid & 63);
+
+    // everything below counts rows from r0, in 32 bits
+    const int n_rows = (int)(r1 - r0);
+    const int32_t* __restrict__ lab = labels + r0;
+    const double* __restrict__ siz = size + r0;
+    const int32_t* __restrict__ xcol = X + r0 * ld + (mine ? g : 0);        // the lane's own column (read when not staged)
+    const int32_t* __restrict__ xtile = X + r0 * ld + gbase + lcol;         // the lane's 16 bytes of a staged row
+
+#pragma unroll 1
+    for (int rt = 0; rt < n_rows; rt += kTile) {
+        const int rows = (n_rows - rt < kTile) ? n_rows - rt : kTile;
+        __syncthreads();                                  // the previous tile has been read
+        if (staged) {
+#pragma unroll
+            for (int i = 0; i < kTile / 4; ++i) {
+                const int tr = lrow + 4 * i;
+                if (tr < rows)
+                    *reinterpret_cast<int4*>(&tile[tr][lcol]) = *reinterpret_cast<const int4*>(xtile + (int64_t)(rt + tr) * ld);
+            }
+        }
+        // a row's size factor, its logarithm and whether it is used
+        if (tid < kTile) {
+            int32_t use = 0;
+            double s = 1.0;
+            if (tid < rows) {
+                const int32_t k = lab[rt + tid];
+                if (k >= K) {
+                    flags |= PROSSTT_AMD_REGRESS_LABEL;
+                } else if (k >= 0) {
+                    const double sv = siz[rt + tid];
+                    if (sv > 0.0 && sv <= kLargest) {
+                        use = 1;
+                        s = sv;
+                    } else {
+                        flags |= PROSSTT_AMD_REGRESS_SIZE;
+                    }
+                }
+            }
+            s_use[tid] = use;
+            s_size[tid] = s;
+            if constexpr (QPASS) s_logs[tid] = log(s);
+        }
+        // the design rows of the tile: 8 x 16 entries, one per thread of the first two waves
+        if (tid < kTile * kMaxP) {
+            const int tr = tid / kMaxP, j = tid % kMaxP;
+            double v = 0.0;
+            if (tr < rows && j < p) {
+                const int32_t k = lab[rt + tr];
+                if (k >= 0 && k < K) v = design[(int64_t)k * ldd + j];
+            }
+            s_design[tr][j] = v;
+        }
+        // the factors of the block's sums
+        if (!QPASS && frow < kTile) {
+            double v = 0.0;
+            if (frow < rows && fj >= 0) {
+                const int32_t k = lab[rt + frow];
+                if (k >= 0 && k < K) {
+                    const double* __restrict__ drow = design + (int64_t)k * ldd;
+                    const double dj = drow[fj];
+                    v = fpair ? dj * drow[fk] : dj;
+                }
+            }
+            // (a sum beyond the block's last has the factor 0: adding 0 v leaves its register as it is, and it is not stored)
+            s_factor[frow][fslot] = (mixed && fpair) ? 0.0 : v;
+            s_second[frow][fslot] = (mixed && fpair) ? v : 0.0;
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int tr = 0; tr < rows; ++tr) {
+            if (!__builtin_amdgcn_readfirstlane(s_use[tr])) continue;      // uniform over the block
+            const int32_t x = staged ? tile[tr][tid] : (mine ? xcol[(int64_t)(rt + tr) * ld] : 0);
+            neg |= x;
+            // (in groups of four: beyond p both factors are +0, and adding their product changes no bit of eta)
+            double eta = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) eta = eta + s_design[tr][j] * c[j];
+            if (p > 4) {
+#pragma unroll
+                for (int j = 4; j < 8; ++j) eta = eta + s_design[tr][j] * c[j];
+            }
+            if (p > 8) {
+#pragma unroll
+                for (int j = 8; j < 12; ++j) eta = eta + s_design[tr][j] * c[j];
+            }
+            if (p > 12) {
+#pragma unroll
+                for (int j = 12; j < 16; ++j) eta = eta + s_design[tr][j] * c[j];
+            }
+            if (x < 0) continue;
+            if (!(__builtin_fabs(eta) <= kEtaMax)) {      // (also a NaN)
+                flags |= PROSSTT_AMD_REGRESS_ETA;
+                continue;
+            }
+            const double mu = s_size[tr] * exp(eta);
+            const double amu = a * mu;
+            const double d = amu + b;
+            if (!(d <= kBig)) {                           // (mu overflowed: infinite, or a NaN from 0 times infinity)
+                flags |= PROSSTT_AMD_REGRESS_ETA;
+                continue;
+            }
+            if constexpr (QPASS) {
+                const double l1 = log1p(amu / b);
+                const double t = a > 0.0 ? l1 / a : mu / b;
+                const double full = ((double)x / b) * ((eta + s_logs[tr]) - (logb + l1)) - t;
+                q = q + (x == 0 ? -t : full);
+                ++used;
+                continue;
+            }
+            const double w = mu / d;
+            const double u = ((double)x - mu) / d;
+            const double second = meat ? u * u : w;
+            if (!(second <= kBig)) {                      // (u u overflowed: only with a = 0 and a mean beyond 1e154)
+                flags |= PROSSTT_AMD_REGRESS_ETA;
+                continue;
+            }
+            if (!mixed) {
+                const double v = nu > 0 ? u : second;
+#pragma unroll
+                for (int i = 0; i < ACC; ++i) acc[i] = acc[i] + s_factor[tr][i] * v;
+            } else {
+                // (one of the two products is a zero of either sign, which changes no bit of a sum that started from +0)
+#pragma unroll
+                for (int i = 0; i < ACC; ++i) acc[i] = (acc[i] + s_factor[tr][i] * u) + s_second[tr][i] * second;
+            }
+        }
+    }
+
+    if (mine) {
+#pragma unroll
+        for (int i = 0; i < ACC; ++i)
+            if (i < na) sums_out[(size_t)i * out_stride] = acc[i];
+        if constexpr (QPASS) {
+            *q_out = q;
+            *used_out = used;
+        }
+    }
+    if (neg < 0) flags |= PROSSTT_AMD_REGRESS_NEGATIVE;
+    if (flags) atomicOr(status_out, flags);
+}
+
+// One thread per (sum, gene) and one per gene: i < (sums + 1) G adds a slab's partial sums -- sums of U, then of I, then Q;
+// (sums + 1) G <= i < (sums + 2) G adds used's.
+__global__ __launch_bounds__(kThreads) void regress_finish_kernel(const double* __restrict__ slab,
+                                                                  const uint32_t* __restrict__ usedslab, int64_t G, int64_t p,
+                                                                  int64_t sums, int64_t row_blocks, double* __restrict__ U,
+                                                                  double* __restrict__ I, double* __restrict__ Q,
+                                                                  uint64_t* __restrict__ used)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    const int64_t SG = (sums + 1) * G;
+    if (i < SG) {
+        double sum = 0.0;
+        for (int64_t rb = 0; rb < row_blocks; ++rb) sum += slab[rb * SG + i];
+        if (i < p * G)
+            U[i] = sum;
+        else if (i < sums * G)
+            I[i - p * G] = sum;
+        else
+            Q[i - sums * G] = sum;
+    } else if (i < SG + G) {
+        const int64_t g = i - SG;
+        uint64_t n = 0;
+        for (int64_t rb = 0; rb < row_blocks; ++rb) n += usedslab[rb * G + g];
+        used[g] = n;
+    }
+}
+
+int check_sizes(int64_t N, int64_t G, int64_t p)
+{
+    if (cells_out_of_range(N) || G < 1)
+        return fail(PROSSTT_AMD_REGRESS_EINVAL, "need 1 <= N < 2^31 and G >= 1 (got N = %lld, G = %lld)", (long long)N,
+                    (long long)G);
+    if (p < 1 || p > kMaxP)
+        return fail(PROSSTT_AMD_REGRESS_EINVAL, "need 1 <= p <= %d coefficients (got %lld)", kMaxP, (long long)p);
+    if (G > ((int64_t(1) << 31) - 1) * kThreads / (kMaxSums + 2))     // (the finishing grid: (sums + 2) G / 256 blocks, for any p)
+        return fail(PROSSTT_AMD_REGRESS_EINVAL, "too many genes for one launch (G = %lld)", (long long)G);
+    return 0;
+}
+
+template <int ACC>
+void launch_pass(bool vec, dim3 grid, hipStream_t st, const int32_t* X, int64_t N, int64_t G, int64_t ld, const double* size,
+                 const int32_t* labels, int32_t K, const double* design, int64_t ldd, int32_t p, const double* coef,
+                 const double* alpha, const double* beta, int32_t meat, int64_t rows, double* slab, uint32_t* usedslab,
+                 uint32_t* status)
+{
+    if (vec)
+        regress_pass_kernel<true, ACC><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, size, labels, K, design, ldd, p, coef, alpha,
+                                                                         beta, meat, rows, slab, usedslab, status);
+    else
+        regress_pass_kernel<false, ACC><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, size, labels, K, design, ldd, p, coef, alpha,
+                                                                          beta, meat, rows, slab, usedslab, status);
+}
+
+}  // namespace
+
+ABI_EXPORT const char* prosstt_amd_regress_last_error(void) { return g_err; }
+
+ABI_EXPORT int prosstt_amd_regress_workspace_bytes(int64_t N, int64_t G, int64_t p, uint64_t* bytes) try
+{
+    if (!bytes) return fail(PROSSTT_AMD_REGRESS_EINVAL, "NULL argument");
+    if (int rc = check_sizes(N, G, p)) return rc;
+    *bytes = geometry(N, G, p).bytes;
+    return 0;
+}
+ABI_CATCH
+
+ABI_EXPORT int prosstt_amd_regress_normal_equations(void* stream, const int32_t* X, int64_t N, int64_t G, int64_t ld,
+                                                    const double* size, const int32_t* labels, int64_t K,
+                                                    const double* design, int64_t ldd, int64_t p, const double* coef,
+                                                    const double* alpha, const double* beta, int32_t meat, int32_t split,
+                                                    void* ws, uint64_t ws_bytes, double* U, double* I_or_M, double* Q,
+                                                    uint64_t* used, uint32_t* status) try
+{
+    if (int rc = check_sizes(N, G, p)) return rc;
+    if (K < 1 || K >= (int64_t(1) << 31))
+        return fail(PROSSTT_AMD_REGRESS_EINVAL, "need 1 <= K < 2^31 rows of the design (got %lld)", (long long)K);
+    if (ld < G) return stride_below_row(ld, G);
+    if (ldd < p) return stride_below_row(ldd, p);
+    // (measured at 50 000 x 20 000: 16 is the fastest split at 14 and at 44 sums, 32 at 152; nothing between was timed)
+    if (split == 0) split = p + p * (p + 1) / 2 <= PROSSTT_AMD_REGRESS_SPLIT_16_MAX_SUMS ? 16 : 32;
+    if (split != 8 && split != 16 && split != 32)
+        return fail(PROSSTT_AMD_REGRESS_EINVAL, "split must be 0, 8, 16 or 32 (got %d)", (int)split);
+    if (!X || !size || !labels || !design || !coef || !alpha || !beta || !U || !I_or_M || !Q || !used || !status)
+        return fail(PROSSTT_AMD_REGRESS_EINVAL, "NULL argument");
+    const Geometry geo = geometry(N, G, p);
+    if (!ws || ws_bytes < geo.bytes) return workspace_too_small(ws_bytes, geo.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)ws;
+    double* slab = (double*)(w + geo.slab);
+    uint32_t* usedslab = (uint32_t*)(w + geo.used);
+    const dim3 grid((unsigned)geo.strips, (unsigned)geo.row_blocks, (unsigned)cdiv(geo.sums, split));
+    const bool vec = aligned(X, ld, 4);
+    const int64_t rows = geo.rows_per_block;
+    if (split == 8)
+        launch_pass<8>(vec, grid, st, X, N, G, ld, size, labels, (int32_t)K, design, ldd, (int32_t)p, coef, alpha, beta, meat, rows,
+                       slab, usedslab, status);
+    else if (split == 16)
+        launch_pass<16>(vec, grid, st, X, N, G, ld, size, labels, (int32_t)K, design, ldd, (int32_t)p, coef, alpha, beta, meat, rows,
+                        slab, usedslab, status);
+    else
+        launch_pass<32>(vec, grid, st, X, N, G, ld, size, labels, (int32_t)K, design, ldd, (int32_t)p, coef, alpha, beta, meat, rows,
+                        slab, usedslab, status);
+    HIP_TRY(hipGetLastError());
+    launch_pass<0>(vec, dim3(grid.x, grid.y, 1), st, X, N, G, ld, size, labels, (int32_t)K, design, ldd, (int32_t)p, coef, alpha, beta,
+                   meat, rows, slab, usedslab, status);
+    HIP_TRY(hipGetLastError());
+    regress_finish_kernel<<<dim3((unsigned)cdiv((geo.sums + 2) * G, kThreads)), dim3(kThreads), 0, st>>>(
+        slab, usedslab, G, p, geo.sums, geo.row_blocks, U, I_or_M, Q, used);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+ABI_CATCH

@@ -1,0 +1,568 @@
+"""
+Regression of the count model on a design, computed where the count matrix lies: on the device.  Per gene
+log(mean / size factor) = design row of the cell . coefficients, under the simulator's own variance law
+(``count_model.get_pr_umi``: variance alpha mu^2 + beta mu), with a covariance for the coefficients, so that a question can be
+asked of the trends along a tree with an error bar:
+
+    X, pt, br, sc = sim.sample_density(t, n, alpha=a, beta=b, out="torch")
+    d = regress.tree_design(t, inner=1)                        # hat functions along the tree, one knot per fork and tip
+    r = regress.regression(X, sc, sim.cell_rows(t, pt, br), d, alpha=a, beta=b)
+    r.wald(d.constant()).pvals_adj                             # which genes change along the tree at all
+    r.wald(d.between("B", "C"))                                # which genes diverge after the fork
+    r.fitted()                                                 # (nodes, genes) means at unit size, what Tree.add_genes takes
+
+``labels`` name the cell's row of the design: its node of the tree (``simulation.cell_rows``, ``mapping.map_cells``), its
+group for ``group_design(K)``, or 0 .. N - 1 for covariates per cell.
+
+The pass over the cells x genes matrix runs in libprosstt_amd_regress.so (include/prosstt_amd_regress.h holds the definition):
+in binary64, for every cell with a label >= 0 and every gene,
+
+    eta = sum_j D[l][j] C[g][j];  mu = s exp(eta);  d = a mu + b;  w = mu / d;  u = (x - mu) / d
+    U[g][j] += D[l][j] u;  I[g][j,k] += (D[l][j] D[l][k]) w;  M[g][j,k] += (D[l][j] D[l][k]) u^2  (``meat``, in I's place)
+    Q[g] += x = 0 ? -T : (x / b) ((eta + log s) - (log b + L1)) - T;  L1 = log1p(a mu / b);  T = a > 0 ? L1 / a : mu / b
+
+U is the quasi-score, I its model-based information and Q the quasi-log-likelihood, concave in the coefficients; with beta = 1
+this is the negative binomial's likelihood equation with known dispersion alpha, with alpha = 0 and beta = 1 the Poisson
+regression.  There is no CPU fallback for the pass: host matrices are refused.  The Fisher scoring (``regression_with``) runs on
+the host in numpy over all genes at once and knows the device only through a callable, so that it is tested against the
+numpy model of the pass without a device.
+"""
+from typing import Any, NamedTuple
+
+import numpy as np
+
+from . import _native, markers
+from . import device as _device
+from .device import _ptr, _torch
+from .fit import _codes, _host
+
+MAX_P = 16                      # PROSSTT_AMD_REGRESS_MAX_P
+SPLITS = (8, 16, 32)            # how many sums of (U, I) a block may keep; 0 is the library's choice
+NEGATIVE, LABEL, PARAMETER, SIZE, COEFFICIENT, ETA = 1, 2, 4, 8, 16, 32          # the bits of the pass's status word
+STATUS_MESSAGES = (
+    (NEGATIVE, "NEGATIVE", _device.NEGATIVE_ENTRY),
+    (LABEL, "LABEL", "a label is not below the number of rows of the design"),
+    (PARAMETER, "PARAMETER", "alpha and beta must be finite with alpha >= 0 and beta >= 1"),
+    (SIZE, "SIZE", "a size factor is not positive and finite (at most 1e150)"),
+    (COEFFICIENT, "COEFFICIENT", "a coefficient is not finite"),
+    (ETA, "ETA", "a linear predictor is not finite or beyond 700 in size, or a mean overflowed"),
+)
+LIMIT = float(np.log(1e7))      # where ``regression`` stops a coefficient by default
+HALVINGS = 8                    # of a step, while the quasi-log-likelihood falls
+
+
+def check_status(bits):
+    """ValueError naming every bit of the pass's status word that is set."""
+    said = ["status bit %s (%d): %s" % (name, bit, text) for bit, name, text in STATUS_MESSAGES if bits & bit]
+    if said:
+        raise ValueError("; ".join(said))
+    if bits:
+        raise RuntimeError("the pass set an unknown status bit (status %d)" % bits)
+
+
+def row_blocks(n_cells, n_genes):
+    """(rows per block, blocks): how the pass cuts the rows of an ``n_cells`` x ``n_genes`` matrix, a function of
+    (N, ceil(G / 256)) alone (``geometry`` of csrc/regress/regress.hip).  A gene's terms are added in ascending row order
+    within a block and the blocks' sums in ascending order; tests/regress_model.py adds in the same order."""
+    strips = -(-int(n_genes) // 256)
+    blocks = min(max(1024 // strips, 1), -(-int(n_cells) // 64))
+    rows = -(-int(n_cells) // blocks)
+    return rows, -(-int(n_cells) // rows)
+
+
+def symmetric(packed, p):
+    """(G, p, p) symmetric from (P2, G): the upper triangle packed by rows, as the pass returns it.  numpy or torch."""
+    j, k = np.triu_indices(p)
+    if isinstance(packed, np.ndarray):
+        full = np.empty((packed.shape[1], p, p), dtype=packed.dtype)
+        full[:, j, k] = packed.T
+        full[:, k, j] = packed.T
+        return full
+    full = packed.new_empty((packed.shape[1], p, p))
+    full[:, j, k] = packed.T
+    full[:, k, j] = packed.T
+    return full
+
+
+class NormalEquations:
+    """The sums of one call (or of several chunks of cells, ``concat``): ``score`` (G, p) the quasi-score U;
+    ``information`` (G, p, p) symmetric, the information I, or the meat M when ``meat``; ``q`` (G,) the quasi-log-likelihood;
+    ``used`` (G,) int64 the entries added; ``n_cells``.  ``score``, ``information`` and ``q`` are numpy arrays, or device
+    tensors for ``out="torch"``."""
+
+    def __init__(self, score, information, q, used, n_cells, meat=False):
+        self.score, self.information, self.q = score, information, q
+        self.used = np.asarray(used, dtype=np.int64)
+        self.n_cells, self.meat = int(n_cells), bool(meat)
+        G = self.used.shape[0]
+        if (len(score.shape) != 2 or score.shape[0] != G or tuple(q.shape) != (G,)
+                or tuple(information.shape) != (G, score.shape[1], score.shape[1])):
+            raise ValueError("score must be (genes, p), information (genes, p, p), q and used (genes,)")
+
+    @property
+    def n_genes(self):
+        return int(self.score.shape[0])
+
+    @property
+    def p(self):
+        return int(self.score.shape[1])
+
+    @staticmethod
+    def concat(parts):
+        """The sums over the cells of all ``parts`` (chunks of one matrix over cells, evaluated at the same coefficients
+        and parameters): added in list order."""
+        parts = list(parts)
+        if not parts:
+            raise ValueError("concat needs at least one NormalEquations")
+        for part in parts:
+            if not isinstance(part, NormalEquations):
+                raise TypeError("concat takes NormalEquations, not %s" % type(part).__name__)
+            if tuple(part.score.shape) != tuple(parts[0].score.shape):
+                raise ValueError("the parts cover different genes or coefficients")
+            if part.meat != parts[0].meat:
+                raise ValueError("the parts mix the information and the meat")
+        score, information, q, used = parts[0].score, parts[0].information, parts[0].q, parts[0].used
+        for part in parts[1:]:
+            score, information, q, used = score + part.score, information + part.information, q + part.q, used + part.used
+        return NormalEquations(score, information, q, used, sum(part.n_cells for part in parts), parts[0].meat)
+
+    def __repr__(self):
+        return "NormalEquations(genes=%d, p=%d, cells=%d%s)" % (self.n_genes, self.p, self.n_cells, ", meat" if self.meat else "")
+
+
+def _design_matrix(design):
+    """The (K, p) float64 host matrix of a ``TreeDesign`` or of anything array-like, or raise."""
+    d = design.matrix if isinstance(design, TreeDesign) else _host(design)
+    d = np.asarray(d)
+    if d.ndim != 2 or d.dtype.kind not in "iuf" or d.shape[0] < 1 or d.shape[1] < 1:
+        raise ValueError("the design must be a (rows, p) array of numbers")
+    if d.shape[1] > MAX_P:
+        raise ValueError("need 1 <= p <= %d coefficients (the design has %d columns)" % (MAX_P, d.shape[1]))
+    if d.shape[0] >= 1 << 31:
+        raise ValueError("the design must have fewer than 2^31 rows")
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    if not np.all(np.isfinite(d)):
+        raise ValueError("the design must be finite")
+    return d
+
+
+def _per_gene(value, n_genes, name):
+    v = np.asarray(_host(value), dtype=np.float64)
+    if v.ndim == 0:
+        v = np.full(n_genes, float(v))
+    if v.shape != (n_genes,):
+        raise ValueError("%s must be a number or one per gene: shape (%d,), not %s" % (name, n_genes, v.shape))
+    return np.ascontiguousarray(v)
+
+
+def _coefficients(coef, n_genes, p):
+    c = np.asarray(_host(coef), dtype=np.float64)
+    if c.shape != (n_genes, p):
+        raise ValueError("coef must be (genes, p) = (%d, %d), not %s" % (n_genes, p, c.shape))
+    return c
+
+
+def _check_split(split):
+    if isinstance(split, (bool, np.bool_)) or split not in (0,) + SPLITS:
+        raise ValueError("split must be 0 (the library's choice), 8, 16 or 32 (got %r)" % (split,))
+    return int(split)
+
+
+class _Pass:
+    """The device side of repeated ``normal_equations`` calls over one matrix: the checked matrix view, the size factors,
+    labels and design on the device, and the workspace."""
+
+    def __init__(self, X, sc, codes, design, who):
+        m = X if isinstance(X, _device.CountMatrix) else _device.CountMatrix(X, who)
+        if m.N < 1 or m.G < 1:
+            raise ValueError("%s needs at least one cell and one gene (got %d x %d)" % (who, m.N, m.G))
+        if m.N >= 1 << 31:
+            raise ValueError("%s takes fewer than 2^31 cells" % who)
+        s = np.asarray(_host(sc), dtype=np.float64)
+        if s.shape != (m.N,):
+            raise ValueError("need one size factor per cell: shape (%d,), not %s" % (m.N, s.shape))
+        self.design = _design_matrix(design)
+        self.K, self.p = self.design.shape
+        self.m = m.on_device()
+        self.lib = _device.need_device("regress")
+        torch = _torch()
+        dev = m.device
+        with torch.cuda.device(dev):
+            rows = markers.codes_in_row_order(codes, m.cell_of_row)
+            self.labels = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
+            self.size = torch.as_tensor(np.ascontiguousarray(markers.codes_in_row_order(s, m.cell_of_row))).to(dev)
+            self.D = torch.as_tensor(self.design).to(dev)
+            self.ws = m.workspace("regress", "prosstt_amd_regress_workspace_bytes", self.p)
+
+    def __call__(self, coef, alpha, beta, meat=False, out="numpy", split=0):
+        m, p = self.m, self.p
+        G = m.G
+        coef = _coefficients(coef, G, p)
+        alpha, beta = _per_gene(alpha, G, "alpha"), _per_gene(beta, G, "beta")
+        P2 = p * (p + 1) // 2
+        torch = _torch()
+        with torch.cuda.device(m.device):
+            par = torch.as_tensor(np.concatenate([np.ascontiguousarray(coef.T), alpha[None, :], beta[None, :]])).to(m.device)
+            sums = torch.empty((p + P2 + 1, G), dtype=torch.float64, device=m.device)        # U, I or M, then Q
+            used = torch.empty(G, dtype=torch.int64, device=m.device)
+            status = torch.zeros(1, dtype=torch.int32, device=m.device)
+            _native.check(self.lib.prosstt_amd_regress_normal_equations(
+                m.stream(), _ptr(m.X), m.N, G, m.ld, _ptr(self.size), _ptr(self.labels), self.K, _ptr(self.D), p, p,
+                _ptr(par[:p]), _ptr(par[p]), _ptr(par[p + 1]), int(bool(meat)), split, _ptr(self.ws), self.ws.numel(),
+                _ptr(sums[:p]), _ptr(sums[p:p + P2]), _ptr(sums[p + P2]), _ptr(used), _ptr(status)), "regress")
+            check_status(int(status.item()))
+            used = used.cpu().numpy()
+            if out == "numpy":
+                sums = sums.cpu().numpy()
+            score = sums[:p].T if out == "numpy" else sums[:p].t()
+            return NormalEquations(score, symmetric(sums[p:p + P2], p), sums[p + P2], used, m.N, meat)
+
+
+def normal_equations(X, sc, labels, design, coef, alpha, beta, *, meat=False, out="numpy", split=0):
+    """``NormalEquations`` of an int32 device count matrix at the coefficients ``coef``.
+
+    ``X`` and ``sc``: as ``fit.loglik`` takes them (a device tensor with unit column stride or a
+    ``device.PresentedCounts``; host size factors per cell in plan order).  ``labels``: one per cell in plan order, the
+    cell's row of ``design`` (integers as they are, names numbered in sorted order, a negative one leaves the cell out;
+    None puts every cell in row 0).  ``design``: (K, p) host numbers with p <= 16, or a ``TreeDesign``.  ``coef``: (G, p).
+    ``alpha``, ``beta``: a number or one per gene.  ``meat``: the sums of (D_j D_k) u^2 in the information's place.
+    ``out``: "numpy", or "torch" for device tensors.  ``split``: how many sums a block keeps, 0 for the library's choice;
+    the result does not depend on it.  Runs on the current stream.
+
+    Raises TypeError for a host matrix or another dtype; ValueError for a CPU tensor, shapes that do not fit, p > 16, a bad
+    ``out`` or ``split``, and for each bit of the pass's status word, with the bit named: a negative count (NEGATIVE), a
+    label that is not below K (LABEL), an inadmissible or non-finite parameter (PARAMETER), a size factor that is not in
+    (0, 1e150] (SIZE), a coefficient that is not finite (COEFFICIENT), a linear predictor beyond 700 in size (ETA)."""
+    if out not in ("numpy", "torch"):
+        raise ValueError("out must be 'numpy' or 'torch'")
+    split = _check_split(split)
+    m = _device.CountMatrix(X, "regress.normal_equations")
+    d = _design_matrix(design)
+    coef = _coefficients(coef, m.G, d.shape[1])
+    alpha, beta = _per_gene(alpha, m.G, "alpha"), _per_gene(beta, m.G, "beta")
+    return _Pass(m, sc, _codes(labels, m.N), d, "regress.normal_equations")(coef, alpha, beta, meat, out, split)
+
+
+# ------------------------------------------------------------------------------------------------------ the designs
+
+class TreeDesign(NamedTuple):
+    """Piecewise-linear hat functions along a tree: ``matrix`` (K, p) float64, row r the weights of node r of
+    ``mapping.node_table(tree)`` on the p knots (not negative, summing to 1, at most two of them above 0); ``knots`` the p
+    pairs (branch name, absolute time) -- knot 0 at the root's first node, then per branch in ``tree.branches`` order its
+    inner knots and the knot at its last node; ``names`` the branches; ``start`` (B,) the knot a branch starts at (knot 0
+    for the root, its parent's end knot otherwise: the fit is continuous across a fork); ``inner`` the inner knots per
+    branch; ``parent`` (B,) the parent branch's index, -1 for the root."""
+    matrix: np.ndarray
+    knots: list
+    names: list
+    start: np.ndarray
+    inner: int
+    parent: np.ndarray
+
+    @property
+    def p(self):
+        return int(self.matrix.shape[1])
+
+    def _branch(self, branch):
+        if branch not in self.names:
+            raise ValueError("branch %r is not a branch of the tree" % (branch,))
+        return self.names.index(branch)
+
+    def branch_knots(self, branch):
+        """The knots of a branch from its start to its end: inner + 2 indices."""
+        b = self._branch(branch)
+        first = 1 + b * (self.inner + 1)
+        return [int(self.start[b])] + list(range(first, first + self.inner + 1))
+
+    def _differences(self, pairs):
+        L = np.zeros((len(pairs), self.p))
+        for row, (plus, minus) in enumerate(pairs):
+            L[row, plus], L[row, minus] = 1.0, -1.0
+        return L
+
+    def constant(self):
+        """(p - 1, p): every knot equals knot 0 -- "does the gene change at all"."""
+        return self._differences([(k, 0) for k in range(1, self.p)])
+
+    def along(self, branch):
+        """(inner + 1, p): consecutive knots of the branch are equal -- "does the gene change along this branch"."""
+        ks = self.branch_knots(branch)
+        return self._differences([(ks[i + 1], ks[i]) for i in range(len(ks) - 1)])
+
+    def between(self, branch_a, branch_b):
+        """(inner + 1, p): the knots of two sibling branches at equal depth are equal -- "do they diverge after the fork"."""
+        a, b = self._branch(branch_a), self._branch(branch_b)
+        if a == b or self.parent[a] != self.parent[b] or self.parent[a] < 0:
+            raise ValueError("between compares two different branches with the same parent (got %r and %r)" % (branch_a, branch_b))
+        return self._differences(list(zip(self.branch_knots(branch_a)[1:], self.branch_knots(branch_b)[1:])))
+
+
+def tree_design(tree, inner=1):
+    """``TreeDesign`` of a tree (only ``topology``, ``time``, ``branches`` are read): one knot at the root, ``inner`` knots
+    inside every branch, equally spaced in time, and one at its end.
+
+    Raises ValueError for ``inner`` that is not an integer >= 0, for more than 16 knots (the message names ``inner`` and the
+    number of branches), and for a branch with too few time steps to tell its knots apart (the matrix would lack rank)."""
+    from .trends import _Nodes
+    if isinstance(inner, (bool, np.bool_)) or not isinstance(inner, (int, np.integer)) or inner < 0:
+        raise ValueError("inner must be an integer >= 0 (got %r)" % (inner,))
+    inner = int(inner)
+    nodes = _Nodes(tree)
+    B = len(nodes.names)
+    p = 1 + B * (inner + 1)
+    if p > MAX_P:
+        raise ValueError("a tree design has 1 + branches (inner + 1) knots: inner = %d on %d branches makes %d, above the "
+                         "%d coefficients a regression takes" % (inner, B, p, MAX_P))
+    parent = np.array([chain[1] if len(chain) > 1 else -1 for chain in nodes.chain], dtype=np.int64)
+    if int((parent < 0).sum()) != 1:
+        raise ValueError("the tree needs exactly one root branch")
+    end = 1 + np.arange(B) * (inner + 1) + inner                 # the knot at a branch's last node
+    start = np.where(parent < 0, 0, end[np.maximum(parent, 0)])
+    matrix = np.zeros((nodes.R, p))
+    knots = [None] * p
+    for b in range(B):
+        t0 = float(nodes.first[b]) if parent[b] < 0 else float(nodes.last[parent[b]])
+        t1 = float(nodes.last[b])
+        ks = [int(start[b])] + list(range(1 + b * (inner + 1), 2 + b * (inner + 1) + inner))
+        times = t0 + (t1 - t0) * np.arange(inner + 2) / (inner + 1)
+        for k, when in zip(ks[(0 if parent[b] < 0 else 1):], times[(0 if parent[b] < 0 else 1):]):
+            knots[k] = (nodes.names[b], float(when))
+        for i in range(int(nodes.length[b])):
+            t = float(nodes.first[b] + i)
+            seg = 0 if t1 == t0 else min(int((t - t0) * (inner + 1) / (t1 - t0)), inner)
+            lo, hi = times[seg], times[seg + 1]
+            right = 1.0 if hi == lo else (t - lo) / (hi - lo)
+            matrix[nodes.offset[b] + i, ks[seg]] += 1.0 - right
+            matrix[nodes.offset[b] + i, ks[seg + 1]] += right
+    if np.linalg.matrix_rank(matrix) < p:
+        raise ValueError("a branch has too few time steps for inner = %d: the nodes do not tell the %d knots apart" % (inner, p))
+    return TreeDesign(matrix, knots, list(nodes.names), start.astype(np.int64), inner, parent)
+
+
+def group_design(K):
+    """The one-hot design of K groups: the (K, K) identity; the coefficients are the groups' log means."""
+    if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or K < 1:
+        raise ValueError("need an integer number of groups >= 1 (got %r)" % (K,))
+    return np.eye(int(K))
+
+
+# ------------------------------------------------------------------------------------------------- the Fisher scoring
+
+class Wald(NamedTuple):
+    """Per gene: ``statistic`` (L c)' (L V L')^-1 (L c), ``df`` the rank of L, ``pvals`` the chi-square upper tail,
+    ``pvals_adj`` Benjamini-Hochberg over the genes that have a statistic (NaN elsewhere)."""
+    statistic: np.ndarray
+    df: np.ndarray
+    pvals: np.ndarray
+    pvals_adj: np.ndarray
+
+
+class Regression(NamedTuple):
+    """What ``regression`` returns, per gene: ``coef`` (G, p); ``cov`` (G, p, p) the inverse information; ``robust_cov``
+    (G, p, p) the sandwich I^-1 M I^-1, or None; ``se`` (G, p) the square roots of the diagonal of ``robust_cov`` if there is
+    one, else of ``cov``; ``q`` the quasi-log-likelihood; ``rounds`` until the gene stopped; ``converged``; ``separated``: a
+    coefficient was stopped at +-``limit`` (a knot or group whose cells hold no count); ``no_counts``: the gene has no count at
+    all (NaN everywhere, not converged); ``design`` the (K, p) matrix."""
+    coef: np.ndarray
+    cov: np.ndarray
+    robust_cov: Any
+    se: np.ndarray
+    q: np.ndarray
+    rounds: np.ndarray
+    converged: np.ndarray
+    separated: np.ndarray
+    no_counts: np.ndarray
+    design: np.ndarray
+
+    def fitted(self, design=None):
+        """(K, G) means at unit size, exp(design . coef): what ``Tree.add_genes`` (cut by branch), ``fit.count_model(means=)``
+        and ``mapping`` take.  ``design``: another (K', p) matrix or ``TreeDesign``; None takes the regression's own."""
+        d = self.design if design is None else _design_matrix(design)
+        if d.shape[1] != self.coef.shape[1]:
+            raise ValueError("the design must have %d columns (got %d)" % (self.coef.shape[1], d.shape[1]))
+        with np.errstate(over="ignore", invalid="ignore"):
+            return np.exp(d @ self.coef.T)
+
+    def wald(self, L):
+        """``Wald`` of the hypothesis L c = 0 per gene, L (r, p) of full row rank, with ``robust_cov`` if there is one."""
+        import scipy.stats
+        L = np.asarray(L, dtype=np.float64)
+        if L.ndim == 1:
+            L = L[None, :]
+        if L.ndim != 2 or L.shape[1] != self.coef.shape[1] or L.shape[0] < 1:
+            raise ValueError("L must be (r, %d), not %s" % (self.coef.shape[1], L.shape))
+        if not np.all(np.isfinite(L)) or np.linalg.matrix_rank(L) < L.shape[0]:
+            raise ValueError("L must be finite and of full row rank")
+        V = self.cov if self.robust_cov is None else self.robust_cov
+        G = self.coef.shape[0]
+        stat = np.full(G, np.nan)
+        ok = np.all(np.isfinite(self.coef), axis=1) & np.all(np.isfinite(V), axis=(1, 2))
+        if ok.any():
+            lc = self.coef[ok] @ L.T                                      # (g, r)
+            lvl = L[None, :, :] @ V[ok] @ L.T[None, :, :]                # (g, r, r)
+            good = np.linalg.cond(lvl) < 1e15
+            value = np.full(lc.shape[0], np.nan)
+            if good.any():
+                solved = np.linalg.solve(lvl[good], lc[good][:, :, None])[:, :, 0]
+                value[good] = np.einsum("gr,gr->g", lc[good], solved)
+            stat[ok] = value
+        have = np.isfinite(stat)
+        df = np.full(G, float(L.shape[0]))
+        pvals = np.full(G, np.nan)
+        pvals[have] = scipy.stats.chi2.sf(stat[have], L.shape[0])
+        adj = np.full(G, np.nan)
+        if have.any():
+            adj[have] = markers.benjamini_hochberg(pvals[have])
+        return Wald(stat, df, pvals, adj)
+
+
+def _check_options(max_rounds, tol, limit):
+    if isinstance(max_rounds, bool) or int(max_rounds) != max_rounds or max_rounds < 1:
+        raise ValueError("need an integer max_rounds >= 1 (got %r)" % (max_rounds,))
+    if not (np.isfinite(tol) and tol > 0):
+        raise ValueError("tol must be positive (got %r)" % (tol,))
+    if not (np.isfinite(limit) and 0 < limit <= 700.0):
+        raise ValueError("limit must be in (0, 700] (got %r)" % (limit,))
+
+
+def _per_gene_or_pinv(batched, information, *rest):
+    """``batched(information, *rest)`` (numpy solves a stack matrix by matrix); where a matrix is singular, the same call
+    gene by gene with the pseudo-inverse for the singular ones alone, so that a gene's result never depends on which other
+    genes are in the call."""
+    try:
+        return batched(information, *rest)
+    except np.linalg.LinAlgError:
+        out = []
+        for g in range(information.shape[0]):
+            one = tuple(a[g:g + 1] for a in (information,) + rest)
+            try:
+                out.append(batched(*one))
+            except np.linalg.LinAlgError:
+                out.append(batched(np.linalg.pinv(one[0], hermitian=True), *one[1:], inverted=True))
+        return np.concatenate(out)
+
+
+def _solve(information, score):
+    """I^-1 U per gene; the pseudo-inverse for a gene whose matrix is singular."""
+    def batched(info, u, inverted=False):
+        return np.einsum("gjk,gk->gj", info, u) if inverted else np.linalg.solve(info, u[:, :, None])[:, :, 0]
+    return _per_gene_or_pinv(batched, information, score)
+
+
+def _inverse(information):
+    """I^-1 per gene; the pseudo-inverse for a gene whose matrix is singular."""
+    def batched(info, inverted=False):
+        return info if inverted else np.linalg.inv(info)
+    return _per_gene_or_pinv(batched, information)
+
+
+def start_coefficients(design, totals, size_total):
+    """(G, p): the least-squares solution of D c = 1 scaled by log(sum x / sum s) per gene (for a design with the constant
+    in its span the fitted means then start at the gene's overall rate); a gene without counts starts at the rate of half
+    a count."""
+    d = _design_matrix(design)
+    ones = np.linalg.lstsq(d, np.ones(d.shape[0]), rcond=None)[0]
+    totals = np.asarray(totals, dtype=np.float64)
+    return np.log(np.maximum(totals, 0.5) / float(size_total))[:, None] * ones[None, :]
+
+
+def regression_with(evaluate, design, totals, size_total, *, robust=False, max_rounds=25, tol=1e-8, limit=LIMIT):
+    """``Regression`` by Fisher scoring through any ``evaluate(coef (G, p), meat) -> NormalEquations`` with host arrays (the
+    device pass, or its numpy model).  ``totals`` (G,): the genes' count sums over the cells used; ``size_total``: the sum
+    of their size factors.
+
+    From ``start_coefficients``; each round steps every gene that has not stopped to coef + t I^-1 U (numpy's batched
+    solve), every coefficient cut to +-``limit``, with t = 1 halved up to 8 times for the genes whose Q fell by more than
+    tol (|Q| + 1) (a smaller fall is the rounding of the sums at the maximum, and a stop); a gene whose Q still falls keeps its
+    coefficients and stops, not converged.  A gene has converged when |Q' - Q| <= tol (|Q'| + 1), and keeps the
+    coefficients it then has.  Deterministic."""
+    _check_options(max_rounds, tol, limit)
+    d = _design_matrix(design)
+    totals = np.asarray(totals, dtype=np.float64)
+    G, p = totals.shape[0], d.shape[1]
+    no_counts = ~(totals > 0)
+    coef = np.clip(start_coefficients(d, totals, size_total), -limit, limit)
+    at = evaluate(coef, False)
+    score, info, q = (np.array(a, dtype=np.float64) for a in (at.score, at.information, at.q))
+    if score.shape != (G, p):
+        raise ValueError("evaluate must return (%d, %d) scores, not %s" % (G, p, score.shape))
+    active = ~no_counts
+    converged = np.zeros(G, dtype=bool)
+    rounds = np.zeros(G, dtype=np.int64)
+    for _ in range(int(max_rounds)):
+        if not active.any():
+            break
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            step = np.where(active[:, None], _solve(np.where(active[:, None, None], info, np.eye(p)), score), 0.0)
+        lost = active & ~np.all(np.isfinite(step), axis=1)              # no finite step: the gene stops where it is
+        active = active & ~lost
+        step[lost] = 0.0
+        t = np.ones(G)
+        falls = active.copy()
+        trial, new = coef, at
+        for _halving in range(HALVINGS + 1):
+            trial = np.where(falls[:, None], np.clip(coef + t[:, None] * step, -limit, limit), trial)
+            new = evaluate(trial, False)
+            with np.errstate(invalid="ignore"):
+                falls = active & ~(np.asarray(new.q) >= q - tol * (np.abs(q) + 1.0))        # (a NaN falls)
+            if not falls.any():
+                break
+            t = np.where(falls, t / 2, t)
+        taken = active & ~falls
+        change = np.abs(np.asarray(new.q) - q)
+        done = taken & (change <= tol * (np.abs(np.asarray(new.q)) + 1.0))
+        coef = np.where(taken[:, None], trial, coef)
+        score = np.where(taken[:, None], np.asarray(new.score), score)
+        info = np.where(taken[:, None, None], np.asarray(new.information), info)
+        q = np.where(taken, np.asarray(new.q), q)
+        rounds = rounds + active
+        converged = converged | done
+        active = taken & ~done
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        cov = _inverse(np.where(no_counts[:, None, None], np.eye(p), info))
+        robust_cov = None
+        if robust:
+            meat = np.asarray(evaluate(coef, True).information, dtype=np.float64)
+            robust_cov = cov @ meat @ cov
+        se = np.sqrt(np.diagonal(cov if robust_cov is None else robust_cov, axis1=1, axis2=2))
+    separated = np.any(np.abs(coef) >= limit, axis=1) & ~no_counts
+    blank = no_counts
+    coef = np.where(blank[:, None], np.nan, coef)
+    cov = np.where(blank[:, None, None], np.nan, cov)
+    if robust_cov is not None:
+        robust_cov = np.where(blank[:, None, None], np.nan, robust_cov)
+    return Regression(coef, cov, robust_cov, np.where(blank[:, None], np.nan, se), np.where(blank, np.nan, q), rounds,
+                      converged & ~blank, separated, no_counts, d)
+
+
+def regression(X, sc, labels, design, *, alpha, beta, robust=False, max_rounds=25, tol=1e-8, limit=LIMIT, split=0):
+    """``Regression`` of an int32 device count matrix on ``design``: per gene the coefficients that solve the quasi-score
+    equation of the count model with the given ``alpha`` and ``beta`` (a number or one per gene; estimate them with
+    ``fit.count_model`` and alternate by hand), their covariance and, with ``robust``, the sandwich covariance from one more
+    pass.
+
+    ``X``, ``sc``, ``labels``, ``design``: as for ``normal_equations``.  ``max_rounds``, ``tol``, ``limit``: ``regression_with``'s.
+    Every round is one pass over the matrix (more when a step is halved); the scoring itself runs on the host.
+
+    Raises what ``normal_equations`` raises; the argument checks come before any device use."""
+    _check_options(max_rounds, tol, limit)
+    split = _check_split(split)
+    m = _device.CountMatrix(X, "regress.regression")
+    d = _design_matrix(design)
+    alpha, beta = _per_gene(alpha, m.G, "alpha"), _per_gene(beta, m.G, "beta")
+    codes = _codes(labels, m.N)
+    s = np.asarray(_host(sc), dtype=np.float64)
+    if s.shape != (m.N,):
+        raise ValueError("need one size factor per cell: shape (%d,), not %s" % (m.N, s.shape))
+    if codes.size and int(codes.max()) >= d.shape[0]:
+        raise ValueError("a label is not below the number of rows of the design (%d)" % d.shape[0])
+    if not np.any(codes >= 0):
+        raise ValueError("regress.regression needs at least one cell with a label >= 0")
+    run = _Pass(m, s, codes, d, "regress.regression")
+    # the genes' count sums over the labelled cells: the exact sums of the grouped pass with every labelled cell in one group
+    # (that pass judges every size factor; the regression judges those of the labelled cells alone, as its header says, so
+    # the cells that are left out go there with a size factor of 1, which no count sum depends on)
+    one = np.where(codes >= 0, 0, -1)
+    totals = np.asarray(markers.group_moments(X, np.where(codes >= 0, s, 1.0), one).count_sum).sum(axis=0)
+    return regression_with(lambda coef, meat: run(coef, alpha, beta, meat, "numpy", split), d, totals,
+                           float(s[codes >= 0].sum()), robust=robust, max_rounds=max_rounds, tol=tol, limit=limit)
