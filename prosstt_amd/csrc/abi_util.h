@@ -8,6 +8,8 @@
 // embed's two products and mapping's pass multiply on the matrix cores: mfma_device.h holds their operand mapping, row load,
 // k-steps and tile map, and the host's choice of a <NT, VEC> instantiation; mapping takes the plumbing and the refusals besides.
 // ptree reads float32 panels, not a count matrix, and takes the plumbing, cdiv, pad and the two refusals.
+// fit's and regress's passes are column kernels (a lane owns one gene): kColumn, kColumnTile, row_blocking and the two
+// refusals of their sizes are here, the device half is column_device.h.
 // The including file defines ABI_EINVAL and ABI_EHIP (its header's error codes) first.
 // (prosstt_amd.hip keeps macros of its own: its ABI has an ENOMEM code and reports e.what().)
 #pragma once
@@ -53,6 +55,8 @@ constexpr int kThreads = 256;               // 4 waves
 constexpr int kStrip = 4 * kThreads;        // genes per block of a strip kernel: one 16-byte load per lane and row
 constexpr int kStripMinRows = 64;           // a strip kernel's block takes at least this many rows (count_summary's batch)
 constexpr int64_t kTargetBlocks = 1024;     // one round of blocks: about four per CU on 256 CUs
+constexpr int kColumn = kThreads;           // genes per block of a column kernel: one per lane
+constexpr int kColumnTile = 8;              // rows of a column kernel's LDS tile: two 16-byte loads per lane
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -77,6 +81,22 @@ inline int workspace_too_small(uint64_t have, size_t need)
     return fail(ABI_EINVAL, "workspace of %llu bytes, %llu needed", (unsigned long long)have, (unsigned long long)need);
 }
 
+// How a kernel whose blocks own `strips` strips of genes cuts N rows: 1024 / strips blocks, at most ceil(N / 64), of equal size.  A
+// function of (N, strips) alone; a gene's sums are added within a block and then over the blocks, so it is part of the result.
+struct RowBlocking {
+    int64_t rows_per_block = 0, row_blocks = 0;
+};
+
+inline RowBlocking row_blocking(int64_t N, int64_t strips)
+{
+    RowBlocking b;
+    // (rounded down: a second round of a few blocks would cost as much as the first)
+    const int64_t rb = clamp64(kTargetBlocks / strips, 1, cdiv(N, kStripMinRows));
+    b.rows_per_block = cdiv(N, rb);
+    b.row_blocks = cdiv(N, b.rows_per_block);
+    return b;
+}
+
 // The grid of a strip kernel: blockIdx.x owns the genes [kStrip x, kStrip (x + 1)), blockIdx.y the rows
 // [rows_per_block y, rows_per_block (y + 1)).  All zeros when G == 0.  (The mapping of a lane to its four genes is
 // strip_device.h's.  count_summary_kernel takes it for g0, the whole-strip test and its stores, with the same loops and
@@ -91,12 +111,26 @@ inline StripGeometry strip_geometry(int64_t N, int64_t G)
     StripGeometry g;
     g.strips = cdiv(G, kStrip);
     if (g.strips > 0) {
-        // (rounded down: a second round of a few blocks would cost as much as the first)
-        const int64_t rb = clamp64(kTargetBlocks / g.strips, 1, cdiv(N, kStripMinRows));
-        g.rows_per_block = cdiv(N, rb);
-        g.row_blocks = cdiv(N, g.rows_per_block);
+        const RowBlocking b = row_blocking(N, g.strips);
+        g.rows_per_block = b.rows_per_block;
+        g.row_blocks = b.row_blocks;
     }
     return g;
+}
+
+// The refusals of a column library's sizes: the matrix, and the finishing grid of threads_per_gene G / 256 blocks.
+inline int column_matrix_refused(int64_t N, int64_t G)
+{
+    if (cells_out_of_range(N) || G < 1)
+        return fail(ABI_EINVAL, "need 1 <= N < 2^31 and G >= 1 (got N = %lld, G = %lld)", (long long)N, (long long)G);
+    return 0;
+}
+
+inline int column_finish_refused(int64_t G, int64_t threads_per_gene)
+{
+    if (G > ((int64_t(1) << 31) - 1) * kThreads / threads_per_gene)
+        return fail(ABI_EINVAL, "too many genes for one launch (G = %lld)", (long long)G);
+    return 0;
 }
 
 }  // namespace

@@ -2,14 +2,12 @@
 // pairs per gene (include/prosstt_amd_fit.h holds the definition; DESIGN section 22 the reasons).
 //
 // Kernels (256 threads = 4 waves each)
-//   fit_loglik_kernel   a block owns a strip of 256 genes, a range of rows and up to kCand = 4 of the C candidates
-//                       (blockIdx.z).  In the arithmetic a lane owns ONE gene: its candidates' (a, b - 1) and their sums stay
-//                       in registers across the rows, and the term's code is there four times, not sixteen (what four genes
-//                       per lane, count_summary's strip, times four candidates would make of the loop).
-//                       <true>  rows that start on 16 bytes: a tile of kTile rows goes through LDS -- wave w loads rows
-//                               w and w + 4 of the tile, a lane 16 bytes (four genes) of each -- and every lane then
-//                               reads its own gene's column of the tile (a last strip of fewer than 256 genes: as <false>)
-//                       <false> any alignment: the lane loads its gene's entry of the row itself (4 bytes, coalesced)
+//   fit_loglik_kernel   a column kernel (column_device.h: a block owns a strip of 256 genes and a range of rows, a lane ONE
+//                       gene; <true> stages tiles of 8 rows through LDS in 16-byte loads, <false> and the last, partial
+//                       strip take 4-byte loads), here with up to kCand = 4 of the C candidates per block (blockIdx.z).
+//                       The lane's candidates' (a, b - 1) and their sums stay in registers across the rows, and the term's
+//                       code is there four times, not sixteen (what four genes per lane, count_summary's strip, times four
+//                       candidates would make of the loop).
 //                       The row's label and size factor are uniform over the block: scalar loads.  The row of means is
 //                       loaded again only when the label differs from the previous row's (cells sorted by label, a
 //                       device.PresentedCounts, load it once per run).  Per entry mu, the x = 0 test and lgamma(x + 1)
@@ -23,12 +21,11 @@
 #define ABI_EINVAL PROSSTT_AMD_FIT_EINVAL
 #define ABI_EHIP PROSSTT_AMD_FIT_EHIP
 #include "../abi_util.h"
+#include "../column_device.h"
 
 namespace {
 
-constexpr int kGenes = kThreads;            // genes per block: one per lane
 constexpr int kCand = 4;                    // candidates per block
-constexpr int kTile = 8;                    // rows of an LDS tile of the aligned kernel: two 16-byte loads per lane
 constexpr int kMaxC = PROSSTT_AMD_FIT_MAX_CANDIDATES;
 constexpr double kLargest = 1e150;         // the largest size factor and the largest mean: their product cannot overflow
 
@@ -42,11 +39,11 @@ struct Geometry {
 Geometry geometry(int64_t N, int64_t G, int64_t C)
 {
     Geometry g;
-    g.strips = cdiv(G, kGenes);
+    g.strips = cdiv(G, kColumn);
     g.chunks = cdiv(C, kCand);
-    const int64_t rb = clamp64(kTargetBlocks / g.strips, 1, cdiv(N, kStripMinRows));
-    g.rows_per_block = cdiv(N, rb);
-    g.row_blocks = cdiv(N, g.rows_per_block);
+    const RowBlocking b = row_blocking(N, g.strips);
+    g.rows_per_block = b.rows_per_block;
+    g.row_blocks = b.row_blocks;
     const size_t cells = (size_t)g.row_blocks * (size_t)G;
     g.ll = 0;
     g.base = g.ll + pad(cells * (size_t)C * 8);
@@ -101,11 +98,7 @@ __device__ __forceinline__ double term(double mu, int32_t x, double a, double bm
 }
 
 // Finite with a >= 0, b >= 1 and a + (b - 1) > 0 (false for a NaN).
-__device__ __forceinline__ bool admissible(double a, double b)
-{
-    const double big = 1.7976931348623157e308;
-    return a >= 0.0 && a <= big && b >= 1.0 && b <= big && a + (b - 1.0) > 0.0;
-}
+__device__ __forceinline__ bool admissible(double a, double b) { return column_admissible(a, b) && a + (b - 1.0) > 0.0; }
 
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void fit_loglik_kernel(const int32_t* __restrict__ X, int64_t N, int64_t G, int64_t ld,
@@ -118,17 +111,13 @@ __global__ __launch_bounds__(kThreads) void fit_loglik_kernel(const int32_t* __r
                                                               double* __restrict__ baseslab, uint32_t* __restrict__ badslab,
                                                               uint32_t* __restrict__ status)
 {
-    __shared__ int32_t tile[VEC ? kTile : 1][kGenes];
-    const int tid = threadIdx.x;
-    const int64_t gbase = (int64_t)blockIdx.x * kGenes;
-    const int64_t g = gbase + tid;
-    const bool mine = g < G;
-    const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
-    const int64_t r1 = (r0 + rows_per_block < N) ? r0 + rows_per_block : N;
+    __shared__ int32_t tile[VEC ? kColumnTile : 1][kColumn];
+    const ColumnLane lane = column_lane<VEC>(N, G, rows_per_block);
+    const int64_t g = lane.g;
+    const bool mine = lane.mine;
     const int64_t c0 = (int64_t)blockIdx.z * kCand;
     const int nc = (int)((C - c0 < kCand) ? C - c0 : kCand);
     const bool first = blockIdx.z == 0;                  // this block also forms base and bad
-    const bool staged = VEC && gbase + kGenes <= G;      // (the last, partial strip reads as the unaligned kernel does)
 
     // The candidates are judged HERE, before any arithmetic on them: an inadmissible or non-finite pair sets the status bit
     // and is replaced by (a, b - 1) = (0, 1), so that theta > 0 and r > 0 hold for everything the loop computes.
@@ -152,9 +141,6 @@ __global__ __launch_bounds__(kThreads) void fit_loglik_kernel(const int32_t* __r
     double base = 0.0, m = 0.0;
     int32_t neg = 0, have_row = -1;
 
-    // the lane's part of a tile's loads: row (wave + 4 i) of the tile, genes 4 * (lane of the wave) .. + 3 of the strip
-    const int lrow = tid >> 6, lcol = 4 * (tid & 63);
-
     // where the lane's sums go, formed here so that the loop need not keep the kernel's arguments for it
     const size_t at = (size_t)blockIdx.y * (size_t)G + (size_t)(mine ? g : 0);
     double* ll_out = llslab + ((size_t)blockIdx.y * (size_t)C + (size_t)c0) * (size_t)G + (size_t)(mine ? g : 0);
@@ -165,24 +151,18 @@ __global__ __launch_bounds__(kThreads) void fit_loglik_kernel(const int32_t* __r
     asm volatile("" : "+v"(ll_out), "+v"(base_out), "+v"(bad_out), "+v"(status_out));
 
     // everything below counts rows from r0, in 32 bits
-    const int n_rows = (int)(r1 - r0);
-    const int32_t* __restrict__ lab = labels + r0;
-    const double* __restrict__ siz = size + r0;
-    const int32_t* __restrict__ xcol = X + r0 * ld + (mine ? g : 0);        // the lane's own column (read when not staged)
-    const int32_t* __restrict__ xtile = X + r0 * ld + gbase + lcol;         // the lane's 16 bytes of a staged row
+    const int32_t* __restrict__ lab = labels + lane.r0;
+    const double* __restrict__ siz = size + lane.r0;
+    const ColumnReader rd = column_reader(lane, X, ld);
+    const int n_rows = rd.n_rows;
     const double* __restrict__ mcol = means + (mine ? g : 0);
 
 #pragma unroll 1
-    for (int rt = 0; rt < n_rows; rt += kTile) {
-        const int rows = (n_rows - rt < kTile) ? n_rows - rt : kTile;
-        if (staged) {
+    for (int rt = 0; rt < n_rows; rt += kColumnTile) {
+        const int rows = (n_rows - rt < kColumnTile) ? n_rows - rt : kColumnTile;
+        if (rd.staged) {
             __syncthreads();                              // the previous tile has been read
-#pragma unroll
-            for (int i = 0; i < kTile / 4; ++i) {
-                const int tr = lrow + 4 * i;
-                if (tr < rows)
-                    *reinterpret_cast<int4*>(&tile[tr][lcol]) = *reinterpret_cast<const int4*>(xtile + (int64_t)(rt + tr) * ld);
-            }
+            column_stage(tile, rd, ld, rt, rows);
             __syncthreads();
         }
 #pragma unroll 1
@@ -198,7 +178,7 @@ __global__ __launch_bounds__(kThreads) void fit_loglik_kernel(const int32_t* __r
                 m = mine ? mcol[(int64_t)k * ldm] : 0.0;
                 if (!(m >= 0.0) || m > kLargest) { flags |= PROSSTT_AMD_FIT_MEAN; m = 0.0; }
             }
-            const int32_t x = staged ? tile[tr][tid] : (mine ? xcol[(int64_t)r * ld] : 0);
+            const int32_t x = column_entry(tile, rd, ld, rt, tr);
             neg |= x;
             if (x < 0) continue;
             const double mu = s * m;                      // (finite: both factors are at most kLargest)
@@ -255,14 +235,10 @@ __global__ __launch_bounds__(kThreads) void fit_finish_kernel(const double* __re
 
 int check_sizes(int64_t N, int64_t G, int64_t C)
 {
-    if (cells_out_of_range(N) || G < 1)
-        return fail(PROSSTT_AMD_FIT_EINVAL, "need 1 <= N < 2^31 and G >= 1 (got N = %lld, G = %lld)", (long long)N,
-                    (long long)G);
+    if (int rc = column_matrix_refused(N, G)) return rc;
     if (C < 1 || C > kMaxC)
         return fail(PROSSTT_AMD_FIT_EINVAL, "need 1 <= C <= %d candidates (got %lld)", kMaxC, (long long)C);
-    if (G > ((int64_t(1) << 31) - 1) * kThreads / (kMaxC + 1))       // (the finishing grid: (C + 1) G / 256 blocks, for any C)
-        return fail(PROSSTT_AMD_FIT_EINVAL, "too many genes for one launch (G = %lld)", (long long)G);
-    return 0;
+    return column_finish_refused(G, kMaxC + 1);                      // (the finishing grid: (C + 1) G / 256 blocks, for any C)
 }
 
 }  // namespace

@@ -3,20 +3,17 @@
 // the reasons).
 //
 // Kernels (256 threads = 4 waves each)
-//   regress_pass_kernel  on fit_loglik_kernel's plan: a block owns a strip of 256 genes, a range of rows and ACC of the
-//                        p + p (p + 1) / 2 sums of (U, I) (blockIdx.z); a lane owns ONE gene, whose coefficients and sums
-//                        stay in registers across the rows.  Every block forms eta, mu, w and u of its entries itself,
+//   regress_pass_kernel  a column kernel (column_device.h: a block owns a strip of 256 genes and a range of rows, a lane ONE
+//                        gene; <VEC = true> stages tiles of 8 rows through LDS in 16-byte loads, <VEC = false> and the
+//                        last, partial strip take 4-byte loads), here with ACC of the p + p (p + 1) / 2 sums of (U, I) per
+//                        block (blockIdx.z); the gene's coefficients and sums stay in registers across the rows.  Every block forms eta, mu, w and u of its entries itself,
 //                        by the same operations, so that the sums do not depend on ACC.  The instantiation ACC = 0 adds Q
 //                        and used and no sum of (U, I): log1p, log and their constants stay out of the other kernels'
 //                        registers.
-//                        What is uniform over the block is formed once per tile of kTile rows and read from LDS by every
+//                        What is uniform over the block is formed once per tile of 8 rows and read from LDS by every
 //                        lane at one address: the row's size factor and its logarithm, whether the row is used, its
 //                        design row, and for each of the block's sums its design factor (D_j for a sum of U, the rounded
 //                        product D_j D_k for one of I).  With ACC = 32 that is one factor per thread and tile.
-//                        <VEC = true>  rows that start on 16 bytes: the tile goes through LDS as in fit_loglik_kernel --
-//                                wave w loads rows w and w + 4, a lane 16 bytes (four genes) of each -- and every lane then
-//                                reads its own gene's column (a last strip of fewer than 256 genes: as <false>)
-//                        <VEC = false> any alignment: the lane loads its gene's entry of the row itself (4 bytes, coalesced)
 //   regress_finish_kernel  adds the blocks' partial sums in ascending block order
 // No atomics but the OR of a status bit.
 #include "../../../include/prosstt_amd_regress.h"
@@ -24,16 +21,14 @@
 #define ABI_EINVAL PROSSTT_AMD_REGRESS_EINVAL
 #define ABI_EHIP PROSSTT_AMD_REGRESS_EHIP
 #include "../abi_util.h"
+#include "../column_device.h"
 
 namespace {
 
-constexpr int kGenes = kThreads;            // genes per block: one per lane
-constexpr int kTile = 8;                    // rows of a tile: two 16-byte loads per lane in the aligned kernel
 constexpr int kMaxP = PROSSTT_AMD_REGRESS_MAX_P;
 constexpr int kMaxSums = kMaxP + kMaxP * (kMaxP + 1) / 2;      // 152
 constexpr double kLargest = 1e150;         // the largest size factor
 constexpr double kEtaMax = 700.0;
-constexpr double kBig = 1.7976931348623157e308;
 
 struct Geometry {
     int64_t strips = 0, row_blocks = 0, rows_per_block = 0, sums = 0;
@@ -41,24 +36,21 @@ struct Geometry {
     size_t bytes = 0;
 };
 
-// The blocking of the rows depends on (N, strips) alone, never on p or the split (fit's rule).
+// The blocking of the rows depends on (N, strips) alone, never on p or the split.
 Geometry geometry(int64_t N, int64_t G, int64_t p)
 {
     Geometry g;
-    g.strips = cdiv(G, kGenes);
+    g.strips = cdiv(G, kColumn);
     g.sums = p + p * (p + 1) / 2;
-    const int64_t rb = clamp64(kTargetBlocks / g.strips, 1, cdiv(N, kStripMinRows));
-    g.rows_per_block = cdiv(N, rb);
-    g.row_blocks = cdiv(N, g.rows_per_block);
+    const RowBlocking b = row_blocking(N, g.strips);
+    g.rows_per_block = b.rows_per_block;
+    g.row_blocks = b.row_blocks;
     const size_t cells = (size_t)g.row_blocks * (size_t)G;
     g.slab = 0;
     g.used = g.slab + pad(cells * (size_t)(g.sums + 1) * 8);
     g.bytes = g.used + pad(cells * 4);
     return g;
 }
-
-// Finite with a >= 0 and b >= 1 (false for a NaN).
-__device__ __forceinline__ bool admissible(double a, double b) { return a >= 0.0 && a <= kBig && b >= 1.0 && b <= kBig; }
 
 template <bool VEC, int ACC>
 __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* __restrict__ X, int64_t N, int64_t G, int64_t ld,
@@ -73,24 +65,22 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
 {
     constexpr bool QPASS = ACC == 0;                      // this instantiation adds Q and used, and no sum of (U, I)
     constexpr int SLOTS = QPASS ? 1 : ACC;
-    static_assert(kThreads % SLOTS == 0 && kTile * SLOTS <= kThreads, "a thread forms at most one factor of a tile, of one sum");
-    __shared__ int32_t tile[VEC ? kTile : 1][kGenes];
-    __shared__ double s_size[kTile], s_logs[kTile];
-    __shared__ int32_t s_use[kTile];
-    __shared__ double s_design[kTile][kMaxP];
-    __shared__ double s_factor[kTile][SLOTS], s_second[kTile][SLOTS];
-    const int tid = threadIdx.x;
-    const int64_t gbase = (int64_t)blockIdx.x * kGenes;
-    const int64_t g = gbase + tid;
-    const bool mine = g < G;
-    const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
-    const int64_t r1 = (r0 + rows_per_block < N) ? r0 + rows_per_block : N;
+    static_assert(kThreads % SLOTS == 0 && kColumnTile * SLOTS <= kThreads, "a thread forms at most one factor of a tile, of one sum");
+    __shared__ int32_t tile[VEC ? kColumnTile : 1][kColumn];
+    __shared__ double s_size[kColumnTile], s_logs[kColumnTile];
+    __shared__ int32_t s_use[kColumnTile];
+    __shared__ double s_design[kColumnTile][kMaxP];
+    __shared__ double s_factor[kColumnTile][SLOTS], s_second[kColumnTile][SLOTS];
     const int sums = p + p * (p + 1) / 2;
     const int a0 = (int)blockIdx.z * ACC;                 // the block's first sum
     const int na = QPASS ? 0 : ((sums - a0 < ACC) ? sums - a0 : ACC);      // how many it has
     const int nu = (p - a0 < 0) ? 0 : ((p - a0 < na) ? p - a0 : na);      // how many of them are sums of U (the first ones)
     const bool mixed = nu > 0 && nu < na;                 // sums of U and of I: two factors per sum, one of them 0
-    const bool staged = VEC && gbase + kGenes <= G;       // (the last, partial strip reads as the unaligned kernel does)
+    // (below the sums' bookkeeping: formed above it, the row loops of the aligned kernels name other scalar registers)
+    const ColumnLane lane = column_lane<VEC>(N, G, rows_per_block);
+    const int tid = lane.tid;
+    const int64_t g = lane.g;
+    const bool mine = lane.mine;
 
     // The gene's parameters and coefficients are judged HERE, before any arithmetic on them (the header's rule).
     uint32_t flags = 0;
@@ -98,7 +88,7 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
     double c[kMaxP], acc[SLOTS];
     if (mine) {
         const double av = alpha[g], bv = beta[g];
-        if (admissible(av, bv)) {
+        if (column_admissible(av, bv)) {
             a = av;
             b = bv;
         } else {
@@ -129,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
     const int frow = tid / SLOTS, fslot = tid % SLOTS;
     int fj = -1, fk = -1;
     bool fpair = false;
-    if (frow < kTile && fslot < na) {
+    if (frow < kColumnTile && fslot < na) {
         const int s = a0 + fslot;
         if (s < p) {
             fj = fk = s;
@@ -145,8 +135,8 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
         }
     }
 
-    // where the lane's sums go, formed here so that the loop need not keep the kernel's arguments for it (fit's device: in
-    // vector registers from here on; kept as scalar arguments, some of them spill)
+    // where the lane's sums go, formed here so that the loop need not keep the kernel's arguments for it (in vector
+    // registers from here on; kept as scalar arguments, some of them spill)
     const size_t gat = (size_t)(mine ? g : 0);
     double* sums_out = slab + ((size_t)blockIdx.y * (size_t)(sums + 1) + (size_t)a0) * (size_t)G + gat;
     double* q_out = slab + ((size_t)blockIdx.y * (size_t)(sums + 1) + (size_t)sums) * (size_t)G + gat;
@@ -155,30 +145,26 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
     size_t out_stride = (size_t)G;
     asm volatile("" : "+v"(sums_out), "+v"(q_out), "+v"(used_out), "+v"(status_out), "+v"(out_stride));
 
-    // the lane's part of a tile's loads: row (wave + 4 i) of the tile, genes 4 * (lane of the wave) .. + 3 of the strip
-    const int lrow = tid >> 6, lcol = 4 * (tid & 63);
-
     // everything below counts rows from r0, in 32 bits
-    const int n_rows = (int)(r1 - r0);
-    const int32_t* __restrict__ lab = labels + r0;
-    const double* __restrict__ siz = size + r0;
-    const int32_t* __restrict__ xcol = X + r0 * ld + (mine ? g : 0);        // the lane's own column (read when not staged)
-    const int32_t* __restrict__ xtile = X + r0 * ld + gbase + lcol;         // the lane's 16 bytes of a staged row
+    const int32_t* __restrict__ lab = labels + lane.r0;
+    const double* __restrict__ siz = size + lane.r0;
+    const ColumnReader rd = column_reader(lane, X, ld);
+    const int n_rows = rd.n_rows;
 
 #pragma unroll 1
-    for (int rt = 0; rt < n_rows; rt += kTile) {
-        const int rows = (n_rows - rt < kTile) ? n_rows - rt : kTile;
+    for (int rt = 0; rt < n_rows; rt += kColumnTile) {
+        const int rows = (n_rows - rt < kColumnTile) ? n_rows - rt : kColumnTile;
         __syncthreads();                                  // the previous tile has been read
-        if (staged) {
+        if (rd.staged) {                                  // (column_stage, written out: column_device.h says why)
 #pragma unroll
-            for (int i = 0; i < kTile / 4; ++i) {
-                const int tr = lrow + 4 * i;
+            for (int i = 0; i < kColumnTile / 4; ++i) {
+                const int tr = rd.lrow + 4 * i;
                 if (tr < rows)
-                    *reinterpret_cast<int4*>(&tile[tr][lcol]) = *reinterpret_cast<const int4*>(xtile + (int64_t)(rt + tr) * ld);
+                    *reinterpret_cast<int4*>(&tile[tr][rd.lcol]) = *reinterpret_cast<const int4*>(rd.xtile + (int64_t)(rt + tr) * ld);
             }
         }
         // a row's size factor, its logarithm and whether it is used
-        if (tid < kTile) {
+        if (tid < kColumnTile) {
             int32_t use = 0;
             double s = 1.0;
             if (tid < rows) {
@@ -200,7 +186,7 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
             if constexpr (QPASS) s_logs[tid] = log(s);
         }
         // the design rows of the tile: 8 x 16 entries, one per thread of the first two waves
-        if (tid < kTile * kMaxP) {
+        if (tid < kColumnTile * kMaxP) {
             const int tr = tid / kMaxP, j = tid % kMaxP;
             double v = 0.0;
             if (tr < rows && j < p) {
@@ -210,7 +196,7 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
             s_design[tr][j] = v;
         }
         // the factors of the block's sums
-        if (!QPASS && frow < kTile) {
+        if (!QPASS && frow < kColumnTile) {
             double v = 0.0;
             if (frow < rows && fj >= 0) {
                 const int32_t k = lab[rt + frow];
@@ -228,7 +214,7 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
 #pragma unroll 1
         for (int tr = 0; tr < rows; ++tr) {
             if (!__builtin_amdgcn_readfirstlane(s_use[tr])) continue;      // uniform over the block
-            const int32_t x = staged ? tile[tr][tid] : (mine ? xcol[(int64_t)(rt + tr) * ld] : 0);
+            const int32_t x = column_entry(tile, rd, ld, rt, tr);
             neg |= x;
             // (in groups of four: beyond p both factors are +0, and adding their product changes no bit of eta)
             double eta = 0.0;
@@ -327,14 +313,10 @@ __global__ __launch_bounds__(kThreads) void regress_finish_kernel(const double* 
 
 int check_sizes(int64_t N, int64_t G, int64_t p)
 {
-    if (cells_out_of_range(N) || G < 1)
-        return fail(PROSSTT_AMD_REGRESS_EINVAL, "need 1 <= N < 2^31 and G >= 1 (got N = %lld, G = %lld)", (long long)N,
-                    (long long)G);
+    if (int rc = column_matrix_refused(N, G)) return rc;
     if (p < 1 || p > kMaxP)
         return fail(PROSSTT_AMD_REGRESS_EINVAL, "need 1 <= p <= %d coefficients (got %lld)", kMaxP, (long long)p);
-    if (G > ((int64_t(1) << 31) - 1) * kThreads / (kMaxSums + 2))     // (the finishing grid: (sums + 2) G / 256 blocks, for any p)
-        return fail(PROSSTT_AMD_REGRESS_EINVAL, "too many genes for one launch (G = %lld)", (long long)G);
-    return 0;
+    return column_finish_refused(G, kMaxSums + 2);                   // (the finishing grid: (sums + 2) G / 256 blocks, for any p)
 }
 
 template <int ACC>

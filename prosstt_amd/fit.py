@@ -28,8 +28,9 @@ from typing import Any, NamedTuple
 
 import numpy as np
 
-from . import _native, markers
+from . import _cellpass, _native, markers
 from . import device as _device
+from ._cellpass import _codes, _host
 from .device import _ptr, _torch
 
 MAX_CANDIDATES = 16             # PROSSTT_AMD_FIT_MAX_CANDIDATES
@@ -84,11 +85,7 @@ class LogLik:
 
 def check_status(bits):
     """ValueError naming every bit of the pass's status word that is set."""
-    said = ["status bit %s (%d): %s" % (name, bit, text) for bit, name, text in STATUS_MESSAGES if bits & bit]
-    if said:
-        raise ValueError("; ".join(said))
-    if bits:
-        raise RuntimeError("the pass set an unknown status bit (status %d)" % bits)
+    _cellpass.check_status(bits, STATUS_MESSAGES)
 
 
 def _parameters(alpha, beta, n_genes):
@@ -108,61 +105,26 @@ def _parameters(alpha, beta, n_genes):
     return out
 
 
-def _host(a):
-    torch = _torch()
-    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
-
-
-def _codes(labels, n_cells):
-    """int64 row of ``means`` per cell in plan order (-1: left out), by ``markers.encode_labels``'s rule without its limit on
-    the number of groups: integers are their own codes, names are numbered in sorted order; None: every cell in row 0."""
-    if labels is None:
-        return np.zeros(n_cells, dtype=np.int64)
-    arr = np.asarray(_host(labels))
-    if arr.shape != (n_cells,):
-        raise ValueError("need one label per cell: shape (%d,), not %s" % (n_cells, arr.shape))
-    if arr.dtype.kind in "iu":
-        if arr.size and int(arr.max()) >= 1 << 31:
-            raise ValueError("labels must be below 2^31")
-        return np.where(arr < 0, -1, arr).astype(np.int64)
-    if arr.dtype.kind in "bf":
-        raise ValueError("labels must be integers or names, not %s" % arr.dtype)
-    return np.unique(arr, return_inverse=True)[1].astype(np.int64).reshape(-1)
-
-
-class _Pass:
+class _Pass(_cellpass.LabelledPass):
     """The device side of repeated ``loglik`` calls over one matrix: the checked matrix view, the size factors, labels and
     means on the device, and the workspace (sized for the largest C)."""
 
     def __init__(self, X, sc, codes, means, who):
-        m = X if isinstance(X, _device.CountMatrix) else _device.CountMatrix(X, who)
-        if m.N < 1 or m.G < 1:
-            raise ValueError("%s needs at least one cell and one gene (got %d x %d)" % (who, m.N, m.G))
-        if m.N >= 1 << 31:
-            raise ValueError("%s takes fewer than 2^31 cells" % who)
-        s = np.asarray(_host(sc), dtype=np.float64)
-        if s.shape != (m.N,):
-            raise ValueError("need one size factor per cell: shape (%d,), not %s" % (m.N, s.shape))
+        super().__init__(X, sc, who)
+        G = self.m.G
         torch = _torch()
         if isinstance(means, torch.Tensor):
-            if means.dim() != 2 or means.shape[1] != m.G or means.shape[0] < 1:
-                raise ValueError("means must be (rows, %d genes), not %s" % (m.G, tuple(means.shape)))
+            if means.dim() != 2 or means.shape[1] != G or means.shape[0] < 1:
+                raise ValueError("means must be (rows, %d genes), not %s" % (G, tuple(means.shape)))
         else:
             means = np.asarray(means, dtype=np.float64)
-            if means.ndim != 2 or means.shape[1] != m.G or means.shape[0] < 1:
-                raise ValueError("means must be (rows, %d genes), not %s" % (m.G, means.shape))
-        self.m = m.on_device()
-        self.lib = _device.need_device("fit")
-        dev = m.device
-        with torch.cuda.device(dev):
-            rows = markers.codes_in_row_order(codes, m.cell_of_row)
-            self.labels = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
-            self.size = torch.as_tensor(np.ascontiguousarray(markers.codes_in_row_order(s, m.cell_of_row))).to(dev)
-            if isinstance(means, torch.Tensor):
-                self.means = means.to(device=dev, dtype=torch.float64).contiguous()
-            else:
-                self.means = torch.as_tensor(np.ascontiguousarray(means)).to(dev)
-            self.ws = m.workspace("fit", "prosstt_amd_fit_workspace_bytes", MAX_CANDIDATES)
+            if means.ndim != 2 or means.shape[1] != G or means.shape[0] < 1:
+                raise ValueError("means must be (rows, %d genes), not %s" % (G, means.shape))
+        dev = self.place(codes, "fit", "prosstt_amd_fit_workspace_bytes", MAX_CANDIDATES)
+        if isinstance(means, torch.Tensor):
+            self.means = means.to(device=dev, dtype=torch.float64).contiguous()
+        else:
+            self.means = torch.as_tensor(np.ascontiguousarray(means)).to(dev)
         self.K = int(self.means.shape[0])
 
     def __call__(self, alpha, beta, out="numpy"):

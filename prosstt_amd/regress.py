@@ -31,10 +31,10 @@ from typing import Any, NamedTuple
 
 import numpy as np
 
-from . import _native, markers
+from . import _cellpass, _native, markers
 from . import device as _device
+from ._cellpass import _codes, _host
 from .device import _ptr, _torch
-from .fit import _codes, _host
 
 MAX_P = 16                      # PROSSTT_AMD_REGRESS_MAX_P
 SPLITS = (8, 16, 32)            # how many sums of (U, I) a block may keep; 0 is the library's choice
@@ -53,17 +53,14 @@ HALVINGS = 8                    # of a step, while the quasi-log-likelihood fall
 
 def check_status(bits):
     """ValueError naming every bit of the pass's status word that is set."""
-    said = ["status bit %s (%d): %s" % (name, bit, text) for bit, name, text in STATUS_MESSAGES if bits & bit]
-    if said:
-        raise ValueError("; ".join(said))
-    if bits:
-        raise RuntimeError("the pass set an unknown status bit (status %d)" % bits)
+    _cellpass.check_status(bits, STATUS_MESSAGES)
 
 
 def row_blocks(n_cells, n_genes):
     """(rows per block, blocks): how the pass cuts the rows of an ``n_cells`` x ``n_genes`` matrix, a function of
-    (N, ceil(G / 256)) alone (``geometry`` of csrc/regress/regress.hip).  A gene's terms are added in ascending row order
-    within a block and the blocks' sums in ascending order; tests/regress_model.py adds in the same order."""
+    (N, ceil(G / 256)) alone (``row_blocking`` of csrc/abi_util.h, which ``fit``'s pass follows too).  A gene's terms are
+    added in ascending row order within a block and the blocks' sums in ascending order; tests/regress_model.py adds in
+    the same order."""
     strips = -(-int(n_genes) // 256)
     blocks = min(max(1024 // strips, 1), -(-int(n_cells) // 64))
     rows = -(-int(n_cells) // blocks)
@@ -168,31 +165,16 @@ def _check_split(split):
     return int(split)
 
 
-class _Pass:
+class _Pass(_cellpass.LabelledPass):
     """The device side of repeated ``normal_equations`` calls over one matrix: the checked matrix view, the size factors,
     labels and design on the device, and the workspace."""
 
     def __init__(self, X, sc, codes, design, who):
-        m = X if isinstance(X, _device.CountMatrix) else _device.CountMatrix(X, who)
-        if m.N < 1 or m.G < 1:
-            raise ValueError("%s needs at least one cell and one gene (got %d x %d)" % (who, m.N, m.G))
-        if m.N >= 1 << 31:
-            raise ValueError("%s takes fewer than 2^31 cells" % who)
-        s = np.asarray(_host(sc), dtype=np.float64)
-        if s.shape != (m.N,):
-            raise ValueError("need one size factor per cell: shape (%d,), not %s" % (m.N, s.shape))
+        super().__init__(X, sc, who)
         self.design = _design_matrix(design)
         self.K, self.p = self.design.shape
-        self.m = m.on_device()
-        self.lib = _device.need_device("regress")
-        torch = _torch()
-        dev = m.device
-        with torch.cuda.device(dev):
-            rows = markers.codes_in_row_order(codes, m.cell_of_row)
-            self.labels = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
-            self.size = torch.as_tensor(np.ascontiguousarray(markers.codes_in_row_order(s, m.cell_of_row))).to(dev)
-            self.D = torch.as_tensor(self.design).to(dev)
-            self.ws = m.workspace("regress", "prosstt_amd_regress_workspace_bytes", self.p)
+        dev = self.place(codes, "regress", "prosstt_amd_regress_workspace_bytes", self.p)
+        self.D = _torch().as_tensor(self.design).to(dev)
 
     def __call__(self, coef, alpha, beta, meat=False, out="numpy", split=0):
         m, p = self.m, self.p
@@ -551,9 +533,7 @@ def regression(X, sc, labels, design, *, alpha, beta, robust=False, max_rounds=2
     d = _design_matrix(design)
     alpha, beta = _per_gene(alpha, m.G, "alpha"), _per_gene(beta, m.G, "beta")
     codes = _codes(labels, m.N)
-    s = np.asarray(_host(sc), dtype=np.float64)
-    if s.shape != (m.N,):
-        raise ValueError("need one size factor per cell: shape (%d,), not %s" % (m.N, s.shape))
+    s = _cellpass.size_factors(sc, m.N)
     if codes.size and int(codes.max()) >= d.shape[0]:
         raise ValueError("a label is not below the number of rows of the design (%d)" % d.shape[0])
     if not np.any(codes >= 0):
