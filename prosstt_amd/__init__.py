@@ -60,6 +60,11 @@ regression of the counts on hat functions along the tree, under the count model'
     r = regress.regression(X, sc, m.node, d, alpha=f.alpha, beta=f.beta)   # r.coef, r.se, r.fitted()
     r.wald(d.constant()).pvals_adj, r.wald(d.between("B", "C")).pvals_adj
 
+How close an inferred trajectory is to the simulated truth (exact sums over all pairs of cells, by pair of true branches):
+
+    from prosstt_amd import evaluate
+    ev = evaluate.trajectory(t, pt, br, lf)           # ev.labels.accuracy, ev.ordering.comparable.gamma, ev.distances.pearson()
+
 or, for unmodified scripts that say ``from prosstt import ...``:
 
     import prosstt_amd; prosstt_amd.install_as_prosstt()

@@ -228,6 +228,13 @@ NEWER_LIBRARIES = {
         "prosstt_amd_regress_normal_equations": _int(vp, vp, i64, i64, i64, vp, vp, i64, vp, i64, i64, vp, vp, vp, i32, i32, vp,
                                                      u64, vp, vp, vp, vp, vp),
     }, "prosstt_amd_regress_last_error"),
+    # scores against the simulated truth: exact sign and tree-distance sums over all pairs of cells, per pair of true classes
+    "evaluate": _Library(_path("PROSSTT_AMD_EVALUATE_LIB", "libprosstt_amd_evaluate.so"), "prosstt_amd_evaluate.h", True, {
+        "prosstt_amd_evaluate_last_error": _text,
+        "prosstt_amd_evaluate_workspace_bytes": _int(i64, i32, i32, _ptr_to(u64)),
+        "prosstt_amd_evaluate_pair_counts": _int(vp, vp, vp, vp, i64, i32, i32, vp, u64, vp, vp),
+        "prosstt_amd_evaluate_pair_moments": _int(vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, u64, vp, vp),
+    }, "prosstt_amd_evaluate_last_error"),
 }
 
 

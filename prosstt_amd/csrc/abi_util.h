@@ -8,6 +8,7 @@
 // embed's two products and mapping's pass multiply on the matrix cores: mfma_device.h holds their operand mapping, row load,
 // k-steps and tile map, and the host's choice of a <NT, VEC> instantiation; mapping takes the plumbing and the refusals besides.
 // ptree reads float32 panels, not a count matrix, and takes the plumbing, cdiv, pad and the two refusals.
+// evaluate reads int32 vectors over the cells and takes the plumbing, cdiv, clamp64, pad and workspace_too_small.
 // fit's and regress's passes are column kernels (a lane owns one gene): kColumn, kColumnTile, row_blocking and the two
 // refusals of their sizes are here, the device half is column_device.h.
 // The including file defines ABI_EINVAL and ABI_EHIP (its header's error codes) first.

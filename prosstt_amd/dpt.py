@@ -1,7 +1,7 @@
 """
 Diffusion pseudotime of the cells and its first branching, computed on the device: the step that ``graph.diffmap`` exists
 for (Haghverdi et al. 2016; scanpy's ``tl.dpt``).  It gives back what the simulation knows, a pseudotime and a branch per
-cell, to compare with ``pt`` and ``br``.
+cell, to compare with ``pt`` and ``br`` (``evaluate.trajectory`` does).
 
     dm = graph.diffmap(neighbors.knn(p.scores, 14, out="torch"), out="torch")
     res = dpt.dpt(dm, root, n_branchings=1)      # res.pseudotime (N,) float64, res.groups (N,) int8, res.tips, res.splits
