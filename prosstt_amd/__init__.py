@@ -65,6 +65,11 @@ How close an inferred trajectory is to the simulated truth (exact sums over all 
     from prosstt_amd import evaluate
     ev = evaluate.trajectory(t, pt, br, lf)           # ev.labels.accuracy, ev.ordering.comparable.gamma, ev.distances.pearson()
 
+An embedding that knows the count model, in PCA's place (GLM-PCA: the low-rank log-bilinear structure the simulator draws from):
+
+    from prosstt_amd import factors
+    fa = factors.glmpca(X, sc, 10, alpha=f.alpha, beta=f.beta)   # fa.scores, fa.loadings, fa.intercept, fa.fitted(), fa.project(X2, sc2)
+
 or, for unmodified scripts that say ``from prosstt import ...``:
 
     import prosstt_amd; prosstt_amd.install_as_prosstt()

@@ -235,6 +235,15 @@ NEWER_LIBRARIES = {
         "prosstt_amd_evaluate_pair_counts": _int(vp, vp, vp, vp, i64, i32, i32, vp, u64, vp, vp),
         "prosstt_amd_evaluate_pair_moments": _int(vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, u64, vp, vp),
     }, "prosstt_amd_evaluate_last_error"),
+    # GLM-PCA factors: per cell the quasi-score, the information and the quasi-log-likelihood of its regression on the genes'
+    # loadings, the half of factors.glmpca's round that regress cannot do without transposing the matrix
+    "factors": _Library(_path("PROSSTT_AMD_FACTORS_LIB", "libprosstt_amd_factors.so"), "prosstt_amd_factors.h", True, {
+        "prosstt_amd_factors_last_error": _text,
+        "prosstt_amd_factors_gene_blocking": _int(i64, i64, _ptr_to(i64)),
+        "prosstt_amd_factors_workspace_bytes": _int(i64, i64, i64, i64, _ptr_to(u64)),
+        "prosstt_amd_factors_cell_equations": _int(vp, vp, i64, i64, i64, vp, vp, vp, i64, i64, vp, vp, vp, i32, i64, vp, u64,
+                                                   vp, vp, vp, vp, vp),
+    }, "prosstt_amd_factors_last_error"),
 }
 
 

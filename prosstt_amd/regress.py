@@ -176,6 +176,16 @@ class _Pass(_cellpass.LabelledPass):
         dev = self.place(codes, "regress", "prosstt_amd_regress_workspace_bytes", self.p)
         self.D = _torch().as_tensor(self.design).to(dev)
 
+    def set_design(self, design):
+        """Another design of the same shape for the calls that follow, without placing the matrix, the labels or the
+        workspace again (``factors.glmpca``: every cell has its own row, whose entries change from round to round)."""
+        d = _design_matrix(design)
+        if d.shape != (self.K, self.p):
+            raise ValueError("the new design must be (%d, %d) as the one before it, not %s" % (self.K, self.p, d.shape))
+        self.design = d
+        with _torch().cuda.device(self.m.device):
+            self.D = _torch().as_tensor(d).to(self.m.device)
+
     def __call__(self, coef, alpha, beta, meat=False, out="numpy", split=0):
         m, p = self.m, self.p
         G = m.G
