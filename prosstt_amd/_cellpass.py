@@ -1,7 +1,8 @@
 """
-What ``fit`` and ``regress`` share on the host: both run a pass over a device count matrix whose cells carry a label (the
-row of a table: of means, of a design) and a size factor, in libraries built on one kernel plan (csrc/column_device.h), and
-both report what the pass refused through a status word.  Internal; every check here comes before any device use.
+What ``fit``, ``regress`` and ``factors`` share on the host: each runs a pass over a device count matrix whose cells carry a
+size factor and, for the first two, a label (the row of a table: of means, of a design), in libraries built on one kernel plan
+(csrc/column_device.h) or one definition of the sums (csrc/quasi_device.h), and each reports what the pass refused through a
+status word.  Internal; every check here comes before any device use.
 """
 import numpy as np
 
@@ -49,27 +50,61 @@ def check_status(bits, messages):
         raise RuntimeError("the pass set an unknown status bit (status %d)" % bits)
 
 
-class LabelledPass:
-    """The device side of repeated calls of a pass over one matrix.  ``__init__`` checks the matrix and the size factors on
-    the host; the subclass checks what it adds and then calls ``place``, the first use of the device."""
+SPLITS = (8, 16, 32)            # how many sums of (U, I) a block of a quasi-likelihood pass may keep; 0 is the library's choice
+
+
+def _check_split(split):
+    if isinstance(split, (bool, np.bool_)) or split not in (0,) + SPLITS:
+        raise ValueError("split must be 0 (the library's choice), 8, 16 or 32 (got %r)" % (split,))
+    return int(split)
+
+
+def _per_gene(value, n_genes, name):
+    v = np.asarray(_host(value), dtype=np.float64)
+    if v.ndim == 0:
+        v = np.full(n_genes, float(v))
+    if v.shape != (n_genes,):
+        raise ValueError("%s must be a number or one per gene: shape (%d,), not %s" % (name, n_genes, v.shape))
+    return np.ascontiguousarray(v)
+
+
+class SizedPass:
+    """The device side of repeated calls of a pass over one matrix whose cells carry a size factor.  ``__init__`` checks the
+    matrix and the size factors on the host; ``place_size`` is the first use of the device."""
 
     def __init__(self, X, sc, who):
         m = X if isinstance(X, _device.CountMatrix) else _device.CountMatrix(X, who)
         if m.N < 1 or m.G < 1:
             raise ValueError("%s needs at least one cell and one gene (got %d x %d)" % (who, m.N, m.G))
-        if m.N >= 1 << 31:
-            raise ValueError("%s takes fewer than 2^31 cells" % who)
+        self._check_bounds(m, who)
         self.m, self._sc = m, size_factors(sc, m.N)
 
-    def place(self, codes, name, query_symbol, *sizes):
-        """The checked matrix view, library ``name``, the labels and size factors in row order on the matrix's device,
-        and the workspace that ``query_symbol`` asks for the matrix and ``sizes``.  Returns the device."""
+    def _check_bounds(self, m, who):
+        if m.N >= 1 << 31:
+            raise ValueError("%s takes fewer than 2^31 cells" % who)
+
+    def place_size(self, name):
+        """The checked matrix view, library ``name``, and the size factors in row order on the matrix's device.  Returns
+        the view."""
         m = self.m.on_device()
         self.lib = _device.need_device(name)
         torch = _torch()
         with torch.cuda.device(m.device):
+            self.size = torch.as_tensor(np.ascontiguousarray(markers.codes_in_row_order(self._sc, m.cell_of_row))).to(m.device)
+        return m
+
+
+class LabelledPass(SizedPass):
+    """A ``SizedPass`` whose cells carry a label besides.  The subclass checks what it adds after ``__init__`` and then calls
+    ``place``, the first use of the device."""
+
+    def place(self, codes, name, query_symbol, *sizes):
+        """``place_size``, the labels in row order on the matrix's device, and the workspace that ``query_symbol`` asks for
+        the matrix and ``sizes``.  Returns the device."""
+        m = self.place_size(name)
+        torch = _torch()
+        with torch.cuda.device(m.device):
             rows = markers.codes_in_row_order(codes, m.cell_of_row)
             self.labels = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.int32)).to(m.device)
-            self.size = torch.as_tensor(np.ascontiguousarray(markers.codes_in_row_order(self._sc, m.cell_of_row))).to(m.device)
             self.ws = m.workspace(name, query_symbol, *sizes)
         return m.device

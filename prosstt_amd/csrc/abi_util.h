@@ -11,6 +11,8 @@
 // evaluate reads int32 vectors over the cells and takes the plumbing, cdiv, clamp64, pad and workspace_too_small.
 // fit's and regress's passes are column kernels (a lane owns one gene): kColumn, kColumnTile, row_blocking and the two
 // refusals of their sizes are here, the device half is column_device.h.
+// factors' pass is regress's with a lane per cell: it takes the plumbing, cdiv, clamp64, pad, aligned, kTargetBlocks and the
+// two refusals; what it shares with regress (the slabs, the split, the finish) is quasi_device.h.
 // The including file defines ABI_EINVAL and ABI_EHIP (its header's error codes) first.
 // (prosstt_amd.hip keeps macros of its own: its ABI has an ENOMEM code and reports e.what().)
 #pragma once

@@ -1,6 +1,7 @@
 // The device half of a column kernel (abi_util.h holds the host half: kColumn, kColumnTile, row_blocking, aligned and the
 // two refusals of a column library's sizes).
-// Internal: included after abi_util.h by fit/fit.hip and regress/regress.hip, not installed under include/.
+// Internal: included after abi_util.h by fit/fit.hip and regress/regress.hip, and by factors/factors.hip for kBig and
+// column_admissible alone (its lane owns a cell, not a gene); not installed under include/.
 //
 // A column kernel reads the int32 count matrix for sums that need many registers per gene.  A block of kThreads lanes owns
 // the kColumn = 256 genes from `gbase` on and the rows [r0, r0 + n_rows) of its row block (row_blocking); a lane owns ONE

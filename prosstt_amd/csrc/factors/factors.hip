@@ -1,22 +1,22 @@
 // libprosstt_amd_factors.so -- the quasi-score, the information and the quasi-log-likelihood of a per-cell regression of a
 // device count matrix on gene loadings (include/prosstt_amd_factors.h holds the definition; DESIGN section 35 the reasons).
 //
+// The arithmetic of an entry, the order of the sums, their split over blockIdx.z (ACC; ACC = 0 adds Q and used), the two
+// tables of factors and the slabs are quasi_device.h's, which regress shares.  What factors adds:
+//
 // Kernels (256 threads = 4 waves each)
 //   factors_pass_kernel  regress's column kernel turned on its side: a block owns 256 cells and one range of
-//                        genes_per_block genes, a lane ONE cell, whose coefficients, size factor and ACC of the
-//                        p + p (p + 1) / 2 sums of (U, I) (blockIdx.z: which) stay in registers across the genes.  The matrix is
+//                        genes_per_block genes (gene_blocking), a lane ONE cell, whose coefficients, size factor and ACC
+//                        sums stay in registers across the genes.  The matrix is
 //                        read along its rows and transposed through LDS: a tile of 256 cells x kTile = 32 genes, loaded in
 //                        16-byte pieces (<VEC = true>, whole tiles) or 4-byte pieces (<VEC = false>, and the ragged last tile
 //                        under either), eight or thirty-two consecutive lanes on one row; the tile's row stride is
 //                        kTile + 1 = 33 words, so the 32 lanes of a half wave write, and later read their own cells'
-//                        entries of one gene from, 32 different banks.  Every block forms eta, mu, w and u of its entries
-//                        itself, by the same operations, so that the sums do not depend on ACC.  The instantiation ACC = 0
-//                        adds Q and used and no sum of (U, I): log1p, log and their constants stay out of the other
-//                        kernels' registers.
+//                        entries of one gene from, 32 different banks.
 //                        What is uniform over the block is formed once per tile of genes and read from LDS by every lane
-//                        at one address: whether the gene is used, its (a, b) and log b, its loadings, and for each of the
-//                        block's sums its factor (L_j for a sum of U, the rounded product L_j L_k for one of I).
-//   factors_finish_kernel  adds the gene blocks' partial sums in ascending block order
+//                        at one address: whether the gene is used (`use`), its (a, b) and log b, its loadings, and for each
+//                        of the block's sums its factor (L_j for a sum of U, the rounded product L_j L_k for one of I).
+//   factors_finish_kernel  quasi_finish over the gene blocks
 // No atomics but the OR of a status bit.
 #include "../../../include/prosstt_amd_factors.h"
 
@@ -24,6 +24,7 @@
 #define ABI_EHIP PROSSTT_AMD_FACTORS_EHIP
 #include "../abi_util.h"
 #include "../column_device.h"
+#include "../quasi_device.h"
 
 namespace {
 
@@ -35,8 +36,7 @@ constexpr int kOwnGenes = 1024;                               // the library's o
 constexpr int kMinTiles = 4;                                   // the library's own blocking gives a block at least this many tiles
 constexpr int64_t kMaxGeneBlocks = PROSSTT_AMD_FACTORS_MAX_GENE_BLOCKS;
 constexpr int64_t kMaxGenesPerBlock = int64_t(1) << 30;
-constexpr double kLargest = 1e150;         // the largest size factor
-constexpr double kEtaMax = 700.0;
+static_assert(PROSSTT_AMD_FACTORS_SPLIT_16_MAX_SUMS == kQuasiSplit16MaxSums, "the header states the shared rule");
 static_assert(kTile % 4 == 0 && kThreads % kTile == 0 && kThreads % (kTile / 4) == 0, "the tile's loads deal rows to whole groups of lanes");
 
 // The library's choice of genes_per_block: about kTargetBlocks blocks over the blocks of cells and no block longer than about
@@ -55,23 +55,19 @@ int64_t gene_blocking(int64_t N, int64_t G)
 
 struct Geometry {
     int64_t cell_blocks = 0, gene_blocks = 0, genes_per_block = 0, sums = 0;
-    size_t slab = 0, used = 0;              // offsets of the slabs [gene_blocks][sums + 1][N] (U, I, then Q) and [gene_blocks][N]
-    size_t bytes = 0;
+    QuasiSlabs at;                          // the slabs [gene_blocks][sums + 1][N] (U, I, then Q) and [gene_blocks][N]
 };
 
 Geometry geometry(int64_t N, int64_t G, int64_t p, int64_t genes_per_block)
 {
     Geometry g;
     g.cell_blocks = cdiv(N, kCells);
-    g.sums = p + p * (p + 1) / 2;
+    g.sums = quasi_sums(p);
     g.genes_per_block = genes_per_block == 0 ? gene_blocking(N, G) : genes_per_block;
     if (g.genes_per_block > cdiv(G, kTile) * kTile) g.genes_per_block = cdiv(G, kTile) * kTile;      // (one block: the same sums)
     if (g.genes_per_block > kMaxGenesPerBlock) g.genes_per_block = kMaxGenesPerBlock;      // (a block counts its genes in 32 bits)
     g.gene_blocks = cdiv(G, g.genes_per_block);
-    const size_t cells = (size_t)g.gene_blocks * (size_t)N;
-    g.slab = 0;
-    g.used = g.slab + pad(cells * (size_t)(g.sums + 1) * 8);
-    g.bytes = g.used + pad(cells * 4);
+    g.at = quasi_slabs(g.gene_blocks, g.sums, N);
     return g;
 }
 
@@ -94,10 +90,7 @@ __global__ __launch_bounds__(kThreads) void factors_pass_kernel(const int32_t* _
     __shared__ double s_factor[kTile][SLOTS], s_second[kTile][SLOTS];
     const int tid = threadIdx.x;
     const int sums = p + p * (p + 1) / 2;
-    const int a0 = (int)blockIdx.z * ACC;                 // the block's first sum
-    const int na = QPASS ? 0 : ((sums - a0 < ACC) ? sums - a0 : ACC);      // how many it has
-    const int nu = (p - a0 < 0) ? 0 : ((p - a0 < na) ? p - a0 : na);      // how many of them are sums of U (the first ones)
-    const bool mixed = nu > 0 && nu < na;                 // sums of U and of I: two factors per sum, one of them 0
+    const auto [a0, na, nu, mixed] = quasi_block_sums<ACC>(p, sums);      // the block's first sum, how many, how many of U
     const int64_t cell0 = (int64_t)blockIdx.x * kCells;
     const int n_cells = (N - cell0 < kCells) ? (int)(N - cell0) : kCells;
     const int64_t cell = cell0 + tid;
@@ -112,7 +105,7 @@ __global__ __launch_bounds__(kThreads) void factors_pass_kernel(const int32_t* _
     double c[kMaxP], acc[SLOTS];
     if (mine) {
         const double sv = size[cell];
-        if (sv > 0.0 && sv <= kLargest) {
+        if (sv > 0.0 && sv <= kQuasiLargest) {
             ok = true;
             s = sv;
         } else {
@@ -140,7 +133,7 @@ __global__ __launch_bounds__(kThreads) void factors_pass_kernel(const int32_t* _
 
     // the sum whose factors this thread forms for the tiles (thread tid: genes tid / SLOTS + i kThreads / SLOTS of the tile,
     // sum a0 + tid % SLOTS): fj == fk for a sum of U (the factor is L[fj]), fj <= fk for one of I (L[fj] L[fk]), fj < 0
-    // beyond the last sum
+    // beyond the last sum (quasi_device.h's order of the sums, written out: DESIGN section 36)
     const int frow = tid / SLOTS, fslot = tid % SLOTS;
     int fj = -1, fk = -1;
     bool fpair = false;
@@ -255,9 +248,7 @@ __global__ __launch_bounds__(kThreads) void factors_pass_kernel(const int32_t* _
                         v = fpair ? lj * lk : lj;
                     }
                 }
-                // (a sum beyond the block's last has the factor 0: adding 0 v leaves its register as it is, and it is not stored)
-                s_factor[tg][fslot] = (mixed && fpair) ? 0.0 : v;
-                s_second[tg][fslot] = (mixed && fpair) ? v : 0.0;
+                quasi_factor_tables(s_factor[tg][fslot], s_second[tg][fslot], mixed, fpair, v);
             }
         }
         __syncthreads();
@@ -268,7 +259,7 @@ __global__ __launch_bounds__(kThreads) void factors_pass_kernel(const int32_t* _
                 if (__builtin_amdgcn_readfirstlane(s_use[tg]) < 0) continue;      // uniform over the block
                 const int32_t x = mytile[tg];
                 neg |= x;
-                // (in groups of four: beyond p both factors are +0, and adding their product changes no bit of eta)
+                // (quasi_device.h's eta, written out: in groups of four; beyond p both factors are +0)
                 double eta = 0.0;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) eta = eta + s_load[tg][j] * c[j];
@@ -285,7 +276,7 @@ __global__ __launch_bounds__(kThreads) void factors_pass_kernel(const int32_t* _
                     for (int j = 12; j < 16; ++j) eta = eta + s_load[tg][j] * c[j];
                 }
                 if (x < 0) continue;
-                if (!(__builtin_fabs(eta) <= kEtaMax)) {      // (also a NaN)
+                if (!(__builtin_fabs(eta) <= kQuasiEtaMax)) {      // (also a NaN)
                     flags |= PROSSTT_AMD_FACTORS_ETA;
                     continue;
                 }
@@ -297,7 +288,7 @@ __global__ __launch_bounds__(kThreads) void factors_pass_kernel(const int32_t* _
                     flags |= PROSSTT_AMD_FACTORS_ETA;
                     continue;
                 }
-                if constexpr (QPASS) {
+                if constexpr (QPASS) {                        // (quasi_device.h's Q term, written out)
                     const double l1 = log1p(amu / b);
                     const double t = a > 0.0 ? l1 / a : mu / b;
                     const double full = ((double)x / b) * ((eta + logs) - (s_logb[tg] + l1)) - t;
@@ -307,12 +298,12 @@ __global__ __launch_bounds__(kThreads) void factors_pass_kernel(const int32_t* _
                 }
                 const double w = mu / d;
                 const double u = ((double)x - mu) / d;
+                // (quasi_device.h's two tables, written out)
                 if (!mixed) {
                     const double v = nu > 0 ? u : w;
 #pragma unroll
                     for (int i = 0; i < ACC; ++i) acc[i] = acc[i] + s_factor[tg][i] * v;
                 } else {
-                    // (one of the two products is a zero of either sign, which changes no bit of a sum that started from +0)
 #pragma unroll
                     for (int i = 0; i < ACC; ++i) acc[i] = (acc[i] + s_factor[tg][i] * u) + s_second[tg][i] * w;
                 }
@@ -335,31 +326,13 @@ __global__ __launch_bounds__(kThreads) void factors_pass_kernel(const int32_t* _
     if (flags) atomicOr(status_out, flags);
 }
 
-// One thread per (sum, cell) and one per cell: i < (sums + 1) N adds a slab's partial sums -- sums of U, then of I, then Q;
-// (sums + 1) N <= i < (sums + 2) N adds used's.
 __global__ __launch_bounds__(kThreads) void factors_finish_kernel(const double* __restrict__ slab,
                                                                   const uint32_t* __restrict__ usedslab, int64_t N, int64_t p,
                                                                   int64_t sums, int64_t gene_blocks, double* __restrict__ U,
                                                                   double* __restrict__ I, double* __restrict__ Q,
                                                                   uint64_t* __restrict__ used)
 {
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    const int64_t SN = (sums + 1) * N;
-    if (i < SN) {
-        double sum = 0.0;
-        for (int64_t gb = 0; gb < gene_blocks; ++gb) sum += slab[gb * SN + i];
-        if (i < p * N)
-            U[i] = sum;
-        else if (i < sums * N)
-            I[i - p * N] = sum;
-        else
-            Q[i - sums * N] = sum;
-    } else if (i < SN + N) {
-        const int64_t cell = i - SN;
-        uint64_t n = 0;
-        for (int64_t gb = 0; gb < gene_blocks; ++gb) n += usedslab[gb * N + cell];
-        used[cell] = n;
-    }
+    quasi_finish(slab, usedslab, N, p, sums, gene_blocks, U, I, Q, used);
 }
 
 int check_sizes(int64_t N, int64_t G, int64_t p, int64_t genes_per_block)
@@ -376,19 +349,6 @@ int check_sizes(int64_t N, int64_t G, int64_t p, int64_t genes_per_block)
         return fail(PROSSTT_AMD_FACTORS_EINVAL, "genes_per_block = %lld cuts %lld genes into more than %lld blocks",
                     (long long)genes_per_block, (long long)G, (long long)kMaxGeneBlocks);
     return 0;
-}
-
-template <int ACC>
-void launch_pass(bool vec, dim3 grid, hipStream_t st, const int32_t* X, int64_t N, int64_t G, int64_t ld, const double* size,
-                 const int32_t* use, const double* loadings, int64_t ldl, int32_t p, const double* coef, const double* alpha,
-                 const double* beta, int64_t genes, double* slab, uint32_t* usedslab, uint32_t* status)
-{
-    if (vec)
-        factors_pass_kernel<true, ACC><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, size, use, loadings, ldl, p, coef, alpha, beta,
-                                                                         genes, slab, usedslab, status);
-    else
-        factors_pass_kernel<false, ACC><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, size, use, loadings, ldl, p, coef, alpha, beta,
-                                                                          genes, slab, usedslab, status);
 }
 
 }  // namespace
@@ -408,7 +368,7 @@ ABI_EXPORT int prosstt_amd_factors_workspace_bytes(int64_t N, int64_t G, int64_t
 {
     if (!bytes) return fail(PROSSTT_AMD_FACTORS_EINVAL, "NULL argument");
     if (int rc = check_sizes(N, G, p, genes_per_block)) return rc;
-    *bytes = geometry(N, G, p, genes_per_block).bytes;
+    *bytes = geometry(N, G, p, genes_per_block).at.bytes;
     return 0;
 }
 ABI_CATCH
@@ -422,31 +382,23 @@ ABI_EXPORT int prosstt_amd_factors_cell_equations(void* stream, const int32_t* X
     if (int rc = check_sizes(N, G, p, genes_per_block)) return rc;
     if (ld < G) return stride_below_row(ld, G);
     if (ldl < p) return stride_below_row(ldl, p);
-    // (regress's rule, whose arithmetic per entry this is; DESIGN section 35 holds what was measured here)
-    if (split == 0) split = p + p * (p + 1) / 2 <= PROSSTT_AMD_FACTORS_SPLIT_16_MAX_SUMS ? 16 : 32;
-    if (split != 8 && split != 16 && split != 32)
-        return fail(PROSSTT_AMD_FACTORS_EINVAL, "split must be 0, 8, 16 or 32 (got %d)", (int)split);
+    if (int rc = quasi_split(p, split)) return rc;
     if (!X || !size || !loadings || !coef || !alpha || !beta || !U || !I || !Q || !used || !status)
         return fail(PROSSTT_AMD_FACTORS_EINVAL, "NULL argument");
     const Geometry geo = geometry(N, G, p, genes_per_block);
-    if (!ws || ws_bytes < geo.bytes) return workspace_too_small(ws_bytes, geo.bytes);
+    if (!ws || ws_bytes < geo.at.bytes) return workspace_too_small(ws_bytes, geo.at.bytes);
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)ws;
-    double* slab = (double*)(w + geo.slab);
-    uint32_t* usedslab = (uint32_t*)(w + geo.used);
-    const dim3 grid((unsigned)geo.cell_blocks, (unsigned)geo.gene_blocks, (unsigned)cdiv(geo.sums, split));
+    double* slab = (double*)((char*)ws + geo.at.slab);
+    uint32_t* usedslab = (uint32_t*)((char*)ws + geo.at.used);
     const bool vec = aligned(X, ld, 4);
-    const int64_t genes = geo.genes_per_block;
-    if (split == 8)
-        launch_pass<8>(vec, grid, st, X, N, G, ld, size, use, loadings, ldl, (int32_t)p, coef, alpha, beta, genes, slab, usedslab, status);
-    else if (split == 16)
-        launch_pass<16>(vec, grid, st, X, N, G, ld, size, use, loadings, ldl, (int32_t)p, coef, alpha, beta, genes, slab, usedslab, status);
-    else
-        launch_pass<32>(vec, grid, st, X, N, G, ld, size, use, loadings, ldl, (int32_t)p, coef, alpha, beta, genes, slab, usedslab, status);
-    HIP_TRY(hipGetLastError());
-    launch_pass<0>(vec, dim3(grid.x, grid.y, 1), st, X, N, G, ld, size, use, loadings, ldl, (int32_t)p, coef, alpha, beta, genes, slab,
-                   usedslab, status);
-    HIP_TRY(hipGetLastError());
+    const auto pass = [&](auto acc) {
+        constexpr int ACC = decltype(acc)::value;         // (0: the Q pass, one layer of blocks)
+        const dim3 grid((unsigned)geo.cell_blocks, (unsigned)geo.gene_blocks, ACC ? (unsigned)cdiv(geo.sums, ACC) : 1u);
+        const auto kernel = vec ? factors_pass_kernel<true, ACC> : factors_pass_kernel<false, ACC>;
+        kernel<<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, size, use, loadings, ldl, (int32_t)p, coef, alpha, beta,
+                                                geo.genes_per_block, slab, usedslab, status);
+    };
+    if (int rc = quasi_passes(split, pass)) return rc;
     factors_finish_kernel<<<dim3((unsigned)cdiv((geo.sums + 2) * N, kThreads)), dim3(kThreads), 0, st>>>(
         slab, usedslab, N, p, geo.sums, geo.gene_blocks, U, I, Q, used);
     HIP_TRY(hipGetLastError());

@@ -2,19 +2,20 @@
 // regression of a device count matrix on a design (include/prosstt_amd_regress.h holds the definition; DESIGN section 31
 // the reasons).
 //
+// The arithmetic of an entry, the order of the sums, their split over blockIdx.z (ACC; ACC = 0 adds Q and used), the two
+// tables of factors and the slabs are quasi_device.h's, which factors shares.  What regress adds:
+//
 // Kernels (256 threads = 4 waves each)
 //   regress_pass_kernel  a column kernel (column_device.h: a block owns a strip of 256 genes and a range of rows, a lane ONE
 //                        gene; <VEC = true> stages tiles of 8 rows through LDS in 16-byte loads, <VEC = false> and the
-//                        last, partial strip take 4-byte loads), here with ACC of the p + p (p + 1) / 2 sums of (U, I) per
-//                        block (blockIdx.z); the gene's coefficients and sums stay in registers across the rows.  Every block forms eta, mu, w and u of its entries itself,
-//                        by the same operations, so that the sums do not depend on ACC.  The instantiation ACC = 0 adds Q
-//                        and used and no sum of (U, I): log1p, log and their constants stay out of the other kernels'
-//                        registers.
+//                        last, partial strip take 4-byte loads); the gene's coefficients, parameters and ACC sums stay in
+//                        registers across the rows.
 //                        What is uniform over the block is formed once per tile of 8 rows and read from LDS by every
 //                        lane at one address: the row's size factor and its logarithm, whether the row is used, its
 //                        design row, and for each of the block's sums its design factor (D_j for a sum of U, the rounded
 //                        product D_j D_k for one of I).  With ACC = 32 that is one factor per thread and tile.
-//   regress_finish_kernel  adds the blocks' partial sums in ascending block order
+//                        `meat` puts u u in w's place in the sums of I.
+//   regress_finish_kernel  quasi_finish over the row blocks
 // No atomics but the OR of a status bit.
 #include "../../../include/prosstt_amd_regress.h"
 
@@ -22,18 +23,17 @@
 #define ABI_EHIP PROSSTT_AMD_REGRESS_EHIP
 #include "../abi_util.h"
 #include "../column_device.h"
+#include "../quasi_device.h"
 
 namespace {
 
 constexpr int kMaxP = PROSSTT_AMD_REGRESS_MAX_P;
 constexpr int kMaxSums = kMaxP + kMaxP * (kMaxP + 1) / 2;      // 152
-constexpr double kLargest = 1e150;         // the largest size factor
-constexpr double kEtaMax = 700.0;
+static_assert(PROSSTT_AMD_REGRESS_SPLIT_16_MAX_SUMS == kQuasiSplit16MaxSums, "the header states the shared rule");
 
 struct Geometry {
     int64_t strips = 0, row_blocks = 0, rows_per_block = 0, sums = 0;
-    size_t slab = 0, used = 0;              // offsets of the slabs [row_blocks][sums + 1][G] (U, I, then Q) and [row_blocks][G]
-    size_t bytes = 0;
+    QuasiSlabs at;                          // the slabs [row_blocks][sums + 1][G] (U, I, then Q) and [row_blocks][G]
 };
 
 // The blocking of the rows depends on (N, strips) alone, never on p or the split.
@@ -41,14 +41,11 @@ Geometry geometry(int64_t N, int64_t G, int64_t p)
 {
     Geometry g;
     g.strips = cdiv(G, kColumn);
-    g.sums = p + p * (p + 1) / 2;
+    g.sums = quasi_sums(p);
     const RowBlocking b = row_blocking(N, g.strips);
     g.rows_per_block = b.rows_per_block;
     g.row_blocks = b.row_blocks;
-    const size_t cells = (size_t)g.row_blocks * (size_t)G;
-    g.slab = 0;
-    g.used = g.slab + pad(cells * (size_t)(g.sums + 1) * 8);
-    g.bytes = g.used + pad(cells * 4);
+    g.at = quasi_slabs(g.row_blocks, g.sums, G);
     return g;
 }
 
@@ -72,10 +69,7 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
     __shared__ double s_design[kColumnTile][kMaxP];
     __shared__ double s_factor[kColumnTile][SLOTS], s_second[kColumnTile][SLOTS];
     const int sums = p + p * (p + 1) / 2;
-    const int a0 = (int)blockIdx.z * ACC;                 // the block's first sum
-    const int na = QPASS ? 0 : ((sums - a0 < ACC) ? sums - a0 : ACC);      // how many it has
-    const int nu = (p - a0 < 0) ? 0 : ((p - a0 < na) ? p - a0 : na);      // how many of them are sums of U (the first ones)
-    const bool mixed = nu > 0 && nu < na;                 // sums of U and of I: two factors per sum, one of them 0
+    const auto [a0, na, nu, mixed] = quasi_block_sums<ACC>(p, sums);      // the block's first sum, how many, how many of U
     // (below the sums' bookkeeping: formed above it, the row loops of the aligned kernels name other scalar registers)
     const ColumnLane lane = column_lane<VEC>(N, G, rows_per_block);
     const int tid = lane.tid;
@@ -116,6 +110,7 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
 
     // the sum whose factors this thread forms for the tiles (thread tid: row tid / ACC of the tile, sum a0 + tid % ACC):
     // fj == fk for a sum of U (the factor is D[fj]), fj <= fk for one of I (D[fj] D[fk]), fj < 0 beyond the last sum
+    // (quasi_device.h's order of the sums, written out: DESIGN section 36)
     const int frow = tid / SLOTS, fslot = tid % SLOTS;
     int fj = -1, fk = -1;
     bool fpair = false;
@@ -173,7 +168,7 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
                     flags |= PROSSTT_AMD_REGRESS_LABEL;
                 } else if (k >= 0) {
                     const double sv = siz[rt + tid];
-                    if (sv > 0.0 && sv <= kLargest) {
+                    if (sv > 0.0 && sv <= kQuasiLargest) {
                         use = 1;
                         s = sv;
                     } else {
@@ -206,9 +201,7 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
                     v = fpair ? dj * drow[fk] : dj;
                 }
             }
-            // (a sum beyond the block's last has the factor 0: adding 0 v leaves its register as it is, and it is not stored)
-            s_factor[frow][fslot] = (mixed && fpair) ? 0.0 : v;
-            s_second[frow][fslot] = (mixed && fpair) ? v : 0.0;
+            quasi_factor_tables(s_factor[frow][fslot], s_second[frow][fslot], mixed, fpair, v);
         }
         __syncthreads();
 #pragma unroll 1
@@ -216,7 +209,7 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
             if (!__builtin_amdgcn_readfirstlane(s_use[tr])) continue;      // uniform over the block
             const int32_t x = column_entry(tile, rd, ld, rt, tr);
             neg |= x;
-            // (in groups of four: beyond p both factors are +0, and adding their product changes no bit of eta)
+            // (quasi_device.h's eta, written out: in groups of four; beyond p both factors are +0)
             double eta = 0.0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) eta = eta + s_design[tr][j] * c[j];
@@ -233,7 +226,7 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
                 for (int j = 12; j < 16; ++j) eta = eta + s_design[tr][j] * c[j];
             }
             if (x < 0) continue;
-            if (!(__builtin_fabs(eta) <= kEtaMax)) {      // (also a NaN)
+            if (!(__builtin_fabs(eta) <= kQuasiEtaMax)) {      // (also a NaN)
                 flags |= PROSSTT_AMD_REGRESS_ETA;
                 continue;
             }
@@ -244,7 +237,7 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
                 flags |= PROSSTT_AMD_REGRESS_ETA;
                 continue;
             }
-            if constexpr (QPASS) {
+            if constexpr (QPASS) {                        // (quasi_device.h's Q term, written out)
                 const double l1 = log1p(amu / b);
                 const double t = a > 0.0 ? l1 / a : mu / b;
                 const double full = ((double)x / b) * ((eta + s_logs[tr]) - (logb + l1)) - t;
@@ -259,12 +252,12 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
                 flags |= PROSSTT_AMD_REGRESS_ETA;
                 continue;
             }
+            // (quasi_device.h's two tables, written out)
             if (!mixed) {
                 const double v = nu > 0 ? u : second;
 #pragma unroll
                 for (int i = 0; i < ACC; ++i) acc[i] = acc[i] + s_factor[tr][i] * v;
             } else {
-                // (one of the two products is a zero of either sign, which changes no bit of a sum that started from +0)
 #pragma unroll
                 for (int i = 0; i < ACC; ++i) acc[i] = (acc[i] + s_factor[tr][i] * u) + s_second[tr][i] * second;
             }
@@ -284,31 +277,13 @@ __global__ __launch_bounds__(kThreads) void regress_pass_kernel(const int32_t* _
     if (flags) atomicOr(status_out, flags);
 }
 
-// One thread per (sum, gene) and one per gene: i < (sums + 1) G adds a slab's partial sums -- sums of U, then of I, then Q;
-// (sums + 1) G <= i < (sums + 2) G adds used's.
 __global__ __launch_bounds__(kThreads) void regress_finish_kernel(const double* __restrict__ slab,
                                                                   const uint32_t* __restrict__ usedslab, int64_t G, int64_t p,
                                                                   int64_t sums, int64_t row_blocks, double* __restrict__ U,
                                                                   double* __restrict__ I, double* __restrict__ Q,
                                                                   uint64_t* __restrict__ used)
 {
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    const int64_t SG = (sums + 1) * G;
-    if (i < SG) {
-        double sum = 0.0;
-        for (int64_t rb = 0; rb < row_blocks; ++rb) sum += slab[rb * SG + i];
-        if (i < p * G)
-            U[i] = sum;
-        else if (i < sums * G)
-            I[i - p * G] = sum;
-        else
-            Q[i - sums * G] = sum;
-    } else if (i < SG + G) {
-        const int64_t g = i - SG;
-        uint64_t n = 0;
-        for (int64_t rb = 0; rb < row_blocks; ++rb) n += usedslab[rb * G + g];
-        used[g] = n;
-    }
+    quasi_finish(slab, usedslab, G, p, sums, row_blocks, U, I, Q, used);
 }
 
 int check_sizes(int64_t N, int64_t G, int64_t p)
@@ -319,20 +294,6 @@ int check_sizes(int64_t N, int64_t G, int64_t p)
     return column_finish_refused(G, kMaxSums + 2);                   // (the finishing grid: (sums + 2) G / 256 blocks, for any p)
 }
 
-template <int ACC>
-void launch_pass(bool vec, dim3 grid, hipStream_t st, const int32_t* X, int64_t N, int64_t G, int64_t ld, const double* size,
-                 const int32_t* labels, int32_t K, const double* design, int64_t ldd, int32_t p, const double* coef,
-                 const double* alpha, const double* beta, int32_t meat, int64_t rows, double* slab, uint32_t* usedslab,
-                 uint32_t* status)
-{
-    if (vec)
-        regress_pass_kernel<true, ACC><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, size, labels, K, design, ldd, p, coef, alpha,
-                                                                         beta, meat, rows, slab, usedslab, status);
-    else
-        regress_pass_kernel<false, ACC><<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, size, labels, K, design, ldd, p, coef, alpha,
-                                                                          beta, meat, rows, slab, usedslab, status);
-}
-
 }  // namespace
 
 ABI_EXPORT const char* prosstt_amd_regress_last_error(void) { return g_err; }
@@ -341,7 +302,7 @@ ABI_EXPORT int prosstt_amd_regress_workspace_bytes(int64_t N, int64_t G, int64_t
 {
     if (!bytes) return fail(PROSSTT_AMD_REGRESS_EINVAL, "NULL argument");
     if (int rc = check_sizes(N, G, p)) return rc;
-    *bytes = geometry(N, G, p).bytes;
+    *bytes = geometry(N, G, p).at.bytes;
     return 0;
 }
 ABI_CATCH
@@ -358,34 +319,23 @@ ABI_EXPORT int prosstt_amd_regress_normal_equations(void* stream, const int32_t*
         return fail(PROSSTT_AMD_REGRESS_EINVAL, "need 1 <= K < 2^31 rows of the design (got %lld)", (long long)K);
     if (ld < G) return stride_below_row(ld, G);
     if (ldd < p) return stride_below_row(ldd, p);
-    // (measured at 50 000 x 20 000: 16 is the fastest split at 14 and at 44 sums, 32 at 152; nothing between was timed)
-    if (split == 0) split = p + p * (p + 1) / 2 <= PROSSTT_AMD_REGRESS_SPLIT_16_MAX_SUMS ? 16 : 32;
-    if (split != 8 && split != 16 && split != 32)
-        return fail(PROSSTT_AMD_REGRESS_EINVAL, "split must be 0, 8, 16 or 32 (got %d)", (int)split);
+    if (int rc = quasi_split(p, split)) return rc;
     if (!X || !size || !labels || !design || !coef || !alpha || !beta || !U || !I_or_M || !Q || !used || !status)
         return fail(PROSSTT_AMD_REGRESS_EINVAL, "NULL argument");
     const Geometry geo = geometry(N, G, p);
-    if (!ws || ws_bytes < geo.bytes) return workspace_too_small(ws_bytes, geo.bytes);
+    if (!ws || ws_bytes < geo.at.bytes) return workspace_too_small(ws_bytes, geo.at.bytes);
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)ws;
-    double* slab = (double*)(w + geo.slab);
-    uint32_t* usedslab = (uint32_t*)(w + geo.used);
-    const dim3 grid((unsigned)geo.strips, (unsigned)geo.row_blocks, (unsigned)cdiv(geo.sums, split));
+    double* slab = (double*)((char*)ws + geo.at.slab);
+    uint32_t* usedslab = (uint32_t*)((char*)ws + geo.at.used);
     const bool vec = aligned(X, ld, 4);
-    const int64_t rows = geo.rows_per_block;
-    if (split == 8)
-        launch_pass<8>(vec, grid, st, X, N, G, ld, size, labels, (int32_t)K, design, ldd, (int32_t)p, coef, alpha, beta, meat, rows,
-                       slab, usedslab, status);
-    else if (split == 16)
-        launch_pass<16>(vec, grid, st, X, N, G, ld, size, labels, (int32_t)K, design, ldd, (int32_t)p, coef, alpha, beta, meat, rows,
-                        slab, usedslab, status);
-    else
-        launch_pass<32>(vec, grid, st, X, N, G, ld, size, labels, (int32_t)K, design, ldd, (int32_t)p, coef, alpha, beta, meat, rows,
-                        slab, usedslab, status);
-    HIP_TRY(hipGetLastError());
-    launch_pass<0>(vec, dim3(grid.x, grid.y, 1), st, X, N, G, ld, size, labels, (int32_t)K, design, ldd, (int32_t)p, coef, alpha, beta,
-                   meat, rows, slab, usedslab, status);
-    HIP_TRY(hipGetLastError());
+    const auto pass = [&](auto acc) {
+        constexpr int ACC = decltype(acc)::value;         // (0: the Q pass, one layer of blocks)
+        const dim3 grid((unsigned)geo.strips, (unsigned)geo.row_blocks, ACC ? (unsigned)cdiv(geo.sums, ACC) : 1u);
+        const auto kernel = vec ? regress_pass_kernel<true, ACC> : regress_pass_kernel<false, ACC>;
+        kernel<<<grid, dim3(kThreads), 0, st>>>(X, N, G, ld, size, labels, (int32_t)K, design, ldd, (int32_t)p, coef, alpha, beta,
+                                                meat, geo.rows_per_block, slab, usedslab, status);
+    };
+    if (int rc = quasi_passes(split, pass)) return rc;
     regress_finish_kernel<<<dim3((unsigned)cdiv((geo.sums + 2) * G, kThreads)), dim3(kThreads), 0, st>>>(
         slab, usedslab, G, p, geo.sums, geo.row_blocks, U, I_or_M, Q, used);
     HIP_TRY(hipGetLastError());

@@ -30,21 +30,16 @@ import numpy as np
 
 from . import _cellpass, _native, markers, regress
 from . import device as _device
-from ._cellpass import _host
+from ._cellpass import _check_split, _host, _per_gene
 from .device import _ptr, _torch
-from .regress import _check_split, _per_gene
 
 MAX_P = 16                      # PROSSTT_AMD_FACTORS_MAX_P
 MAX_K = MAX_P - 1               # the intercept is one of a half's coefficients
 TILE_GENES = 32                 # PROSSTT_AMD_FACTORS_TILE_GENES
-NEGATIVE, PARAMETER, SIZE, COEFFICIENT, ETA = 1, 4, 8, 16, 32          # the bits of the pass's status word (regress's values)
-STATUS_MESSAGES = (
-    (NEGATIVE, "NEGATIVE", _device.NEGATIVE_ENTRY),
-    (PARAMETER, "PARAMETER", "alpha and beta must be finite with alpha >= 0 and beta >= 1"),
-    (SIZE, "SIZE", "a size factor is not positive and finite (at most 1e150)"),
-    (COEFFICIENT, "COEFFICIENT", "a coefficient or a loading is not finite"),
-    (ETA, "ETA", "a linear predictor is not finite or beyond 700 in size, or a mean overflowed"),
-)
+# the bits of the pass's status word are regress's, without LABEL; a loading is a coefficient of the other half
+NEGATIVE, PARAMETER, SIZE, COEFFICIENT, ETA = regress.NEGATIVE, regress.PARAMETER, regress.SIZE, regress.COEFFICIENT, regress.ETA
+STATUS_MESSAGES = tuple((bit, name, "a coefficient or a loading is not finite" if bit == COEFFICIENT else text)
+                        for bit, name, text in regress.STATUS_MESSAGES if bit != regress.LABEL)
 HALVINGS = 8                    # of a step, while the penalised quasi-log-likelihood falls
 # the defaults of ``glmpca``, chosen by tools/factors_calibration.py among penalties 1, 10, 50 (DESIGN section 35 holds the table)
 PENALTY = 50.0
@@ -168,27 +163,24 @@ def _check_genes_per_block(genes_per_block):
     return int(g)
 
 
-class _CellPass:
+class _CellPass(_cellpass.SizedPass):
     """The device side of repeated ``cell_equations`` calls over one matrix: the checked matrix view, the size factors on the
     device in row order, and the workspace.  ``__init__`` checks on the host; the first call is the first use of the device."""
 
     def __init__(self, X, sc, who):
-        m = X if isinstance(X, _device.CountMatrix) else _device.CountMatrix(X, who)
-        if m.N < 1 or m.G < 1:
-            raise ValueError("%s needs at least one cell and one gene (got %d x %d)" % (who, m.N, m.G))
+        super().__init__(X, sc, who)
+        self.lib, self._ws = None, {}
+
+    def _check_bounds(self, m, who):
         if m.N >= 1 << 31 or m.G >= 1 << 31:
             raise ValueError("%s takes fewer than 2^31 cells and fewer than 2^31 genes" % who)
-        self.m, self._sc = m, _cellpass.size_factors(sc, m.N)
-        self.lib, self._ws = None, {}
 
     def _place(self, p, genes_per_block):
         m, torch = self.m, _torch()
         if self.lib is None:
-            m.on_device()
-            self.lib = _device.need_device("factors")
-            with torch.cuda.device(m.device):
-                self.size = torch.as_tensor(np.ascontiguousarray(markers.codes_in_row_order(self._sc, m.cell_of_row))).to(m.device)
-                if m.cell_of_row is not None:
+            self.place_size("factors")
+            if m.cell_of_row is not None:
+                with torch.cuda.device(m.device):
                     self.row_of_cell = torch.as_tensor(_device.inverse_permutation(m.cell_of_row)).to(m.device)
         if (p, genes_per_block) not in self._ws:
             self._ws = {(p, genes_per_block): m.workspace("factors", "prosstt_amd_factors_workspace_bytes", p, genes_per_block)}

@@ -33,11 +33,10 @@ import numpy as np
 
 from . import _cellpass, _native, markers
 from . import device as _device
-from ._cellpass import _codes, _host
+from ._cellpass import SPLITS, _check_split, _codes, _host, _per_gene          # (SPLITS, _check_split, _per_gene: factors' too)
 from .device import _ptr, _torch
 
 MAX_P = 16                      # PROSSTT_AMD_REGRESS_MAX_P
-SPLITS = (8, 16, 32)            # how many sums of (U, I) a block may keep; 0 is the library's choice
 NEGATIVE, LABEL, PARAMETER, SIZE, COEFFICIENT, ETA = 1, 2, 4, 8, 16, 32          # the bits of the pass's status word
 STATUS_MESSAGES = (
     (NEGATIVE, "NEGATIVE", _device.NEGATIVE_ENTRY),
@@ -143,26 +142,11 @@ def _design_matrix(design):
     return d
 
 
-def _per_gene(value, n_genes, name):
-    v = np.asarray(_host(value), dtype=np.float64)
-    if v.ndim == 0:
-        v = np.full(n_genes, float(v))
-    if v.shape != (n_genes,):
-        raise ValueError("%s must be a number or one per gene: shape (%d,), not %s" % (name, n_genes, v.shape))
-    return np.ascontiguousarray(v)
-
-
 def _coefficients(coef, n_genes, p):
     c = np.asarray(_host(coef), dtype=np.float64)
     if c.shape != (n_genes, p):
         raise ValueError("coef must be (genes, p) = (%d, %d), not %s" % (n_genes, p, c.shape))
     return c
-
-
-def _check_split(split):
-    if isinstance(split, (bool, np.bool_)) or split not in (0,) + SPLITS:
-        raise ValueError("split must be 0 (the library's choice), 8, 16 or 32 (got %r)" % (split,))
-    return int(split)
 
 
 class _Pass(_cellpass.LabelledPass):
