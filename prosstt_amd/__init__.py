@@ -70,6 +70,13 @@ An embedding that knows the count model, in PCA's place (GLM-PCA: the low-rank l
     from prosstt_amd import factors
     fa = factors.glmpca(X, sc, 10, alpha=f.alpha, beta=f.beta)   # fa.scores, fa.loadings, fa.intercept, fa.fitted(), fa.project(X2, sc2)
 
+A knob chosen without a truth: split every count at random into a train and a test part (binomial thinning; also the way to
+lower the depth of a matrix), fit on one, score on the other:
+
+    from prosstt_amd import thin
+    sp = thin.split(X, 0.5, seed=1)                   # sp.train + sp.test == X; sp.sizes(sc); thin.fold, thin.downsample
+    thin.rank_curve(X, sc, (1, 2, 3, 5, 8), alpha=f.alpha, beta=f.beta).best
+
 or, for unmodified scripts that say ``from prosstt import ...``:
 
     import prosstt_amd; prosstt_amd.install_as_prosstt()

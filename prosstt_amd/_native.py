@@ -244,6 +244,13 @@ NEWER_LIBRARIES = {
         "prosstt_amd_factors_cell_equations": _int(vp, vp, i64, i64, i64, vp, vp, vp, i64, i64, vp, vp, vp, i32, i64, vp, u64,
                                                    vp, vp, vp, vp, vp),
     }, "prosstt_amd_factors_last_error"),
+    # binomial thinning: the part [lo, hi) of every count by THIN-1, a pure function of (seed, cell, gene), and its complement;
+    # what thin.split, thin.fold and thin.downsample are made of
+    "thin": _Library(_path("PROSSTT_AMD_THIN_LIB", "libprosstt_amd_thin.so"), "prosstt_amd_thin.h", True, {
+        "prosstt_amd_thin_last_error": _text,
+        "prosstt_amd_thin_plan": _int(i64, i64, vp, i64, vp, i64, vp, i64, _ptr_to(i32), _ptr_to(i64), _ptr_to(i64), _ptr_to(i64)),
+        "prosstt_amd_thin_interval": _int(vp, vp, i64, i64, i64, u64, vp, i64, i64, u32, u32, vp, vp, vp, i64, vp, i64, vp),
+    }, "prosstt_amd_thin_last_error"),
 }
 
 

@@ -4,7 +4,7 @@
 // Internal: included by every HIP library but the sampler (Makefile: the rows that list it), each a single translation
 // unit, and not installed under include/.  The libraries that read no count matrix (knn, graph, layout, tsne, dpt, cluster)
 // use the error plumbing, cdiv, clamp64, pad, aligned and the two refusals only, and include graph_util.h after this file
-// for the refusals and grid rules they share.  The strip kernels are those of stats, embed, hvg, markers, ranks and trends.
+// for the refusals and grid rules they share.  The strip kernels are those of stats, embed, hvg, markers, ranks, trends and thin.
 // embed's two products and mapping's pass multiply on the matrix cores: mfma_device.h holds their operand mapping, row load,
 // k-steps and tile map, and the host's choice of a <NT, VEC> instantiation; mapping takes the plumbing and the refusals besides.
 // ptree reads float32 panels, not a count matrix, and takes the plumbing, cdiv, pad and the two refusals.

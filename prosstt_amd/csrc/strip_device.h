@@ -1,6 +1,7 @@
 // The device half of a strip kernel (abi_util.h holds the host half: kStrip, strip_geometry, aligned).
 // Internal: included after abi_util.h by stats/count_summary.hip, embed/embed.hip, hvg/hvg.hip, markers/markers.hip,
-// ranks/ranks.hip and trends/trends.hip, not installed under include/.
+// ranks/ranks.hip, trends/trends.hip and thin/thin.hip (which writes a matrix and keeps its store_row4), not installed under
+// include/.
 //
 // A block of kThreads lanes owns the kStrip genes from `gbase` on, and a lane owns four of them.  VEC (every row can be read
 // in 16-byte pieces: aligned(X, ld, 4)): the four are contiguous from g0 = gbase + 4 tid, so that a row of a whole strip is
